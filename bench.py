@@ -10,7 +10,13 @@ the per-GPU shard of BASELINE config C3 (128 images per GPU) with the parameters
 libsiftgpu, over xGMI) only for the per-image feature-count all-gather; torch.distributed
 (gloo, host) is the rendezvous.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run sets up, warms up, times the steps and prints the line.  --full adds every other
+measurement to the same line: the single-image C2 protocol, the C4 tiles, the C5 matcher, the
+host-in / host-out stream, the CPU baselines and the lookup of the committed counter profile
+(the --no-* options drop single legs of it).  --dump-outputs DIR writes what the last timed
+step computed as .npy files, for comparing two builds output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -28,6 +34,7 @@ import sgpu  # noqa: E402  (loads libsiftgpu.so before torch: one HIP runtime, /
 from sgpu_types import default_options  # noqa: E402
 from sift_synth import synth_batch_fast, synth_descriptors, synth_guided_scene, quantize  # noqa: E402
 
+DUMP_DESC_BYTES = 48 << 20     # --dump-outputs: descriptor rows kept (all files stay under 64 MB)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md, chip-level parameters (spec)
 I8_MFMA_PEAK_TOPS = 5000.0     # dense i8 MFMA = 2x the ~2.5 PF bf16 rate (same guide)
 
@@ -39,6 +46,32 @@ def geometry_sum(w, h, octaves):
         ww >>= 1
         hh >>= 1
     return tot
+
+
+def dump_outputs(ctx, out_dir, B, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float32
+    / float64 .npy files in out_dir (rank r of a multi-GPU run adds _rank<r> to the names).
+    counts: features per image; keys: the (x, y, scale, orientation) rows of every image, in
+    image order; descriptors: the 128-float rows of a fixed sample of the images (a seeded
+    permutation, taken in its order while the rows fit DUMP_DESC_BYTES), in the order of
+    descriptor_images; descriptor_images: the indices of those images."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    counts = np.fromiter((ctx.count(i) for i in range(B)), np.float64, B)
+    keys = [ctx.features(i, descriptors=False)[0] for i in range(B)]
+    picked, desc, room = [], [], DUMP_DESC_BYTES
+    for i in np.random.default_rng(1234).permutation(B).tolist():
+        room -= int(counts[i]) * 128 * 4
+        if room < 0:
+            break
+        picked.append(i)
+        desc.append(ctx.features(i)[1])
+    out = {"counts": counts,
+           "keys": np.concatenate(keys) if keys else np.zeros((0, 4), np.float32),
+           "descriptors": np.concatenate(desc) if desc else np.zeros((0, 128), np.float32),
+           "descriptor_images": np.asarray(picked, np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
 
 
 def self_launch(n):
@@ -72,6 +105,13 @@ def main():
     ap.add_argument("--workload", default="c3", choices=["c3", "c4"],
                     help="c3: 128 x 1920x1080 per GPU (-no 4), the headline; c4: BASELINE "
                          "configs[3], 4096x4096 tiles with 6 octaves, as the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (C2, C4, C5 matcher, "
+                         "host-in / host-out stream, CPU baselines, committed-profile lookup); "
+                         "the --no-* options below drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's feature counts, keys and "
+                         "a fixed sample of the descriptors to DIR/<name>.npy")
     ap.add_argument("--no-c4", action="store_true", help="skip the C4 sub-measurement")
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip the host-in / host-out (PCIe-inclusive) sub-measurement")
@@ -89,6 +129,11 @@ def main():
                          "(the real run); gloo: host all-gather (rehearsal: ranks may then "
                          "share one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: the headline alone
+        args.no_c4 = args.no_e2e = args.no_cpu_baseline = args.no_c2 = args.no_match = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -197,6 +242,9 @@ def main():
         dist.all_reduce(f)
         feats = int(f.item())
 
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, B, rank, world)
+
     verify = None
     if args.verify:
         # outside the timed region: the last step's results of every image of every rank, as
@@ -228,7 +276,9 @@ def main():
     pyr_bytes = 48.0 * sumN * B * args.steps          # 48 B per pyramid px
     achieved = pyr_bytes / (pyr_ms * 1e-3) / 1e9 if pyr_ms > 0 else 0.0
 
-    traffic, prof_note = profiled_traffic(B, W, H, args.octaves)
+    # the committed counter profile of this tree, if there is one: looked up under --full
+    lookup = (B, W, H, args.octaves) if args.full else None
+    traffic, prof_note = profiled_traffic(lookup)
     if args.workload == "c4":
         workload = (f"C4: {B} x {W}x{H} u8 gray tiles per GPU per step, -fo 0 -no "
                     f"{args.octaves} -d 3 (BASELINE.json configs[3], HBM-bound pyramid stress)")
@@ -288,7 +338,7 @@ def main():
     if det_ms > 0:
         det_s = det_ms * 1e-3 / args.steps
         alg = (48.0 + 4.0 * (3 + 3)) * sumN * B
-        moved, src = detection_traffic(B, W, H, args.octaves)
+        moved, src = detection_traffic(lookup)
         result["full_detection"] = {
             "ms_per_step": det_ms / args.steps,
             "algorithmic_bytes_per_step": alg,
@@ -327,15 +377,18 @@ def main():
     ctx.close()
 
 
-def matching_profile(B, W, H, octaves):
-    """The newest committed calibrated rocprofv3 summary (tests/profile_kernels.sh +
+def matching_profile(workload):
+    """workload: (B, W, H, octaves), or None in a run without --full, which looks nothing up.
+    The newest committed calibrated rocprofv3 summary (tests/profile_kernels.sh +
     tests/pmc_summary.py) of this workload whose source digest (tests/prof_common.py) equals the
     tree being benchmarked, as (summary, note); (None, reason) when there is none -- counters of
     older kernels are never divided by the current kernels' time."""
+    if workload is None:
+        return None, "not looked up (bench.py --full does)"
+    if workload != (128, 1920, 1080, 4):
+        return None, "no profile for this workload"
     import glob
     from prof_common import source_digest
-    if (B, W, H, octaves) != (128, 1920, 1080, 4):
-        return None, "no profile for this workload"
     here = source_digest()
     newest = None
     for path in reversed(sorted(glob.glob(os.path.join(ROOT, "profiles", "*_summary.json")))):
@@ -354,12 +407,12 @@ def matching_profile(B, W, H, octaves):
                   "no calibrated profile summary committed")
 
 
-def profiled_traffic(B, W, H, octaves):
+def profiled_traffic(workload):
     """HBM bytes per Gaussian launch from the committed calibrated summary of this tree and
     workload, or None.  The summary's FETCH_SIZE / WRITE_SIZE are corrected per access width with
     the committed calibration (tests/pmc_calib.sh; MI355X_MICROARCH.md: FETCH_SIZE counts 1/2 of
     a 16-B-per-lane streaming read)."""
-    s, note = matching_profile(B, W, H, octaves)
+    s, note = matching_profile(workload)
     if s is None:
         return None, note
     try:
@@ -371,10 +424,10 @@ def profiled_traffic(B, W, H, octaves):
         return None, "malformed summary: " + note
 
 
-def detection_traffic(B, W, H, octaves):
+def detection_traffic(workload):
     """HBM bytes per extract of the Gaussian and extremum kernels from the committed calibrated
     summary of this tree (see matching_profile), or None."""
-    s, note = matching_profile(B, W, H, octaves)
+    s, note = matching_profile(workload)
     if s is None:
         return None, note
     h = s["hbm_bytes_per_extract"]

@@ -1,7 +1,8 @@
 // abi_check.cpp -- vtable / data-layout compatibility check of libsiftgpu.so.
 //
-// Compiled twice by tests/test_capi.py: once against include/SiftGPU.h and, when the reference
-// checkout is present (this container only), against the reference's own SiftGPU/SiftGPU.h.
+// Compiled twice: by tests/test_capi.py against include/SiftGPU.h and, where a checkout of the
+// reference is present, by oracle/Makefile against the reference's own SiftGPU/SiftGPU.h (the
+// program lands in oracle/_ref/, which git ignores, and tests/test_capi.py runs it from there).
 // The program loads the library the way TestWin/SimpleSIFT.cpp:92-121 does (dlopen + dlsym of
 // the extern "C" factories) and calls virtual methods that need no GPU, so a slot mismatch
 // between the two headers shows up as a wrong result or a crash.

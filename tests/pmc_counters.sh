@@ -5,7 +5,7 @@ TAG=$1; shift
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-A="--steps 1 --warmup 0 --no-cpu-baseline --no-match"
+A="--full --steps 1 --warmup 0 --no-cpu-baseline --no-match"
 i=0
 for SET in "$@"; do
   i=$((i+1))

@@ -14,7 +14,9 @@ from sgpu_types import SgpuOptions, default_options
 from sift_synth import quantize
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+# binaries that build() compiles from a checkout of the reference, where one is present
+# (oracle/Makefile); they travel with the tree, the checkout need not
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
 
 
 def _exported(path):
@@ -126,28 +128,29 @@ def _compile(src, out, include):
 
 @pytest.mark.parametrize("header", ["ours", "reference"])
 def test_cpp_abi_layout(tmp_path, header):
-    inc = os.path.join(ROOT, "include")
     if header == "reference":
-        inc = os.path.join(REF, "SiftGPU")
-        if not os.path.exists(os.path.join(inc, "SiftGPU.h")):
-            pytest.skip("reference checkout not present (GPU box)")
-    exe = str(tmp_path / "abi_check")
-    _compile(os.path.join(ROOT, "tests", "abi", "abi_check.cpp"), exe, inc)
+        # tests/abi/abi_check.cpp against the reference's own SiftGPU.h
+        exe = os.path.join(REF_BIN, "abi_check_ref")
+        if not os.path.exists(exe):
+            pytest.skip("oracle/_ref/abi_check_ref not built: build() found no reference checkout")
+    else:
+        exe = str(tmp_path / "abi_check")
+        _compile(os.path.join(ROOT, "tests", "abi", "abi_check.cpp"), exe,
+                 os.path.join(ROOT, "include"))
     r = subprocess.run([exe, sgpu.LIB_PATH], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "abi ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
-def test_reference_simplesift_compiles_against_our_header(tmp_path):
-    src = os.path.join(REF, "TestWin", "SimpleSIFT.cpp")
-    if not os.path.exists(src):
-        pytest.skip("reference checkout not present (GPU box)")
-    # SimpleSIFT.cpp includes "../SiftGPU/SiftGPU.h": give it a tree whose SiftGPU/ is ours
-    (tmp_path / "SiftGPU").mkdir()
-    (tmp_path / "TestWin").mkdir()
-    os.symlink(os.path.join(ROOT, "include", "SiftGPU.h"), tmp_path / "SiftGPU" / "SiftGPU.h")
-    os.symlink(src, tmp_path / "TestWin" / "SimpleSIFT.cpp")
-    # compile-only check (-fsyntax-only): the file is never copied into the repository
-    r = subprocess.run(["g++", "-std=c++11", "-fsyntax-only", "-fpermissive", "-w",
-                        "-DSIFTGPU_DLL_RUNTIME", str(tmp_path / "TestWin" / "SimpleSIFT.cpp")],
-                       capture_output=True, text=True, cwd=tmp_path)
-    assert r.returncode == 0, r.stderr[-2000:]
+def test_reference_simplesift_compiles_against_our_header():
+    """The reference's TestWin/SimpleSIFT.cpp compiles and links against include/SiftGPU.h:
+    build() does that wherever the reference checkout is present (oracle/Makefile, which fails
+    the build when the file does not compile) and leaves the program under oracle/_ref/; the
+    file itself is never copied into the repository.  The program wants its own image files and
+    a GPU, so it is not run here: tests/abi/simple_sift_replica.cpp is the run-time check."""
+    exe = os.path.join(REF_BIN, "simple_sift_ref")
+    if not os.path.exists(exe):
+        pytest.skip("oracle/_ref/simple_sift_ref not built: build() found no reference checkout")
+    assert os.access(exe, os.X_OK)
+    # it resolves the factories at run time (SIFTGPU_DLL_RUNTIME), as the library exports them
+    undefined = subprocess.check_output(["nm", "-D", "--undefined-only", exe], text=True)
+    assert "dlsym" in undefined and "CreateNewSiftGPU" not in undefined
