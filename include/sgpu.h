@@ -226,6 +226,44 @@ int sgpu_match_sharded(sgpu_ctx* ctx, const uint8_t* d1, int ns, int row_begin,
 
 /* float -> u8 quantization of SiftMatchCU::SetDescriptors (SiftMatchCU.cpp:94-99), host side. */
 void sgpu_quantize_descriptors(const float* d, size_t count, uint8_t* out);
+/* The same quantization on the device: d [ndesc][128] floats -> out [ndesc][128] u8, byte for
+ * byte what sgpu_quantize_descriptors writes (the add in double).  SGPU_INPUT_HOST: both are host
+ * pointers (upload, one kernel, download); SGPU_INPUT_DEVICE: both are device pointers. */
+int sgpu_quantize_descriptors_gpu(sgpu_ctx* ctx, const float* d, size_t ndesc, uint8_t* out,
+                                  int flags);
+/* Device pointer to the last extract's descriptors as u8 [total][128], in the order of
+ * sgpu_device_features (a multi-part batch goes through the same gathered buffer).  Quantized on
+ * first request, in one launch that also prepares the matcher's forms of the sets, and kept until
+ * the next extract, sgpu_extract_keypoints or options change.  SGPU_EINVAL when the context holds
+ * no last batch (e.g. after sgpu_extract_stream) or descriptors are off. */
+int sgpu_feature_descriptors_u8(sgpu_ctx* ctx, const uint8_t** desc_u8);
+/* Copy image i's u8 descriptors (128 bytes each) to host memory: a quarter of the float
+ * download of sgpu_copy_features.  Same error conditions as sgpu_feature_descriptors_u8. */
+int sgpu_copy_features_u8(sgpu_ctx* ctx, int image, uint8_t* desc);
+
+/* Grouped pair matcher: many set pairs of one descriptor buffer in one call.  desc is u8
+ * [set_offsets[nsets]][128] (host, or device with SGPU_INPUT_DEVICE; exactly that many bytes are
+ * read), set s = rows [set_offsets[s], set_offsets[s + 1]); set_offsets and set_pairs are host
+ * arrays.  Pair p = (a, b) gives exactly sgpu_match(set a, set b, distmax, ratiomax,
+ * mutual_best_match, max_match): {i, j} in ascending i, at most max_match per pair.  The pairs'
+ * results are concatenated in pair order into out_pairs [cap][2], out_counts[p] = pair p's count;
+ * returns the total.  More than cap matches: SGPU_ERANGE, all counts complete, the matches of
+ * the leading pairs that fit written (sgpu_extract_stream's convention).  Empty sets give count
+ * 0; (a, a), repeated pairs and both orders are legal; an index outside [0, nsets) or decreasing
+ * offsets give SGPU_EINVAL.  No reference counterpart: SiftMatchGPU matches one pair per
+ * SetDescriptors + GetSiftMatch (SiftGPU.h:300-311).  The number of kernel launches, copies and
+ * synchronisations does not depend on npairs; sgpu_last_timing's times[8] is its device time. */
+int sgpu_match_batch(sgpu_ctx* ctx, const uint8_t* desc, const int64_t* set_offsets, int nsets,
+                     const int* set_pairs /* [npairs][2] */, int npairs,
+                     float distmax, float ratiomax, int mutual_best_match, int max_match,
+                     int* out_pairs /* [cap][2] */, int64_t cap, int* out_counts /* [npairs] */,
+                     int flags);
+/* sgpu_match_batch over the last extract: the sets are the batch's images, their descriptors
+ * sgpu_feature_descriptors_u8's, so no descriptor crosses PCIe.  SGPU_EINVAL under the same
+ * conditions as sgpu_feature_descriptors_u8. */
+int sgpu_match_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, float distmax,
+                      float ratiomax, int mutual_best_match, int max_match,
+                      int* out_pairs, int64_t cap, int* out_counts);
 
 /* Timing of the last call: stage times in milliseconds measured with HIP events
  * (SiftGPU::_timing, SiftPyramid.cpp:48-56).  times[0..7] =

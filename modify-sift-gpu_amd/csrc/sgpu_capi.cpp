@@ -25,6 +25,7 @@
 
 #include "../../include/sgpu.h"
 #include "sift_kernels.h"
+#include "sift_match_plan.h"
 #include "sift_params.h"
 
 namespace {
@@ -227,6 +228,15 @@ struct sgpu_ctx {
                                            // (sgpu_debug_set_match_prune; SGPU_MATCH_PRUNE=off)
     std::vector<int> h_match;
     bool dist_ready = false;
+    // grouped pair matcher (sgpu_match_batch): uploaded descriptors and their s8 form / row sums,
+    // the planner's tables, chunk partials, decisions, [counts npairs][offsets npairs + 1], pairs
+    DevBuf b_desc, b_s8, b_sums, b_plan, b_part, b_dec, b_cnt, b_out;
+    sgplan::Plan b_hplan;
+    std::vector<unsigned char> b_tables;   // the tables as uploaded (alive until the call's sync)
+    // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
+    // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
+    DevBuf q_in, q_out, f_u8, f_s8, f_sums;
+    bool f_ready = false;
     // multi-GPU: RCCL communicator of this context's device (sgpu_comm_*)
     ncclComm_t comm = nullptr;
     int comm_ranks = 0, comm_rank = 0;
@@ -371,6 +381,7 @@ int sgpu_ctx_set_options(sgpu_ctx* ctx, const sgpu_options* opt) {
     if (o.dog_level_num < 1 || o.dog_level_num > 6) return ctx->fail(SGPU_EINVAL, "dog_level_num must be 1..6");
     if (o.max_dimension < 8) return ctx->fail(SGPU_EINVAL, "max_dimension must be >= 8");
     ctx->opt = o;
+    ctx->f_ready = false;   // the cached u8 descriptors belong to the previous options
     sgp::Options po;
     po.filter_width_factor = o.filter_width_factor;
     po.dog_level_num = o.dog_level_num;
@@ -539,7 +550,9 @@ int sgpu_ctx_destroy(sgpu_ctx* ctx) {
     DevBuf* bufs[] = {&ctx->input, &ctx->input2, &ctx->duo_trash, &ctx->all_keys, &ctx->all_desc, &ctx->gray, &ctx->pre, &ctx->m_d1, &ctx->m_d2, &ctx->m_s1, &ctx->m_s2,
                       &ctx->m_part, &ctx->m_terms, &ctx->m_match, &ctx->m_dist, &ctx->m_mask, &ctx->m_loc,
                       &ctx->m_colpart, &ctx->m_cols, &ctx->m_prune, &ctx->m_s1c,
-                      &ctx->c_buf};
+                      &ctx->b_desc, &ctx->b_s8, &ctx->b_sums, &ctx->b_plan, &ctx->b_part, &ctx->b_dec,
+                      &ctx->b_cnt, &ctx->b_out, &ctx->q_in, &ctx->q_out, &ctx->f_u8, &ctx->f_s8,
+                      &ctx->f_sums, &ctx->c_buf};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i <= T_N; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -1129,6 +1142,7 @@ static int plan_batch(sgpu_ctx* ctx, int n, int w, int h) {
     ctx->w = plan.ds ? plan.w : w;
     ctx->h = plan.h;
     ctx->gathered = false;
+    ctx->f_ready = false;
     return SGPU_OK;
 }
 
@@ -1149,6 +1163,7 @@ static int abandon_batch(sgpu_ctx* ctx, int rc) {
     ctx->batch = 0;
     ctx->img_off.clear();
     ctx->gathered = false;
+    ctx->f_ready = false;
     return rc;
 }
 
@@ -1576,6 +1591,7 @@ int sgpu_extract_keypoints(sgpu_ctx* ctx, int image, const float* keys, int num,
     }
     for (int i = 0; i <= ctx->batch; i++) ctx->img_off[i] = i > image ? num : 0;
     ctx->gathered = false;
+    ctx->f_ready = false;
     return SGPU_OK;
 }
 
@@ -2216,6 +2232,224 @@ int sgpu_device_features(sgpu_ctx* ctx, const float** keys, const float** descri
 
 void sgpu_quantize_descriptors(const float* d, size_t count, uint8_t* out) {
     for (size_t i = 0; i < count; ++i) out[i] = (uint8_t)(int)(512 * d[i] + 0.5);
+}
+
+int sgpu_quantize_descriptors_gpu(sgpu_ctx* ctx, const float* d, size_t ndesc, uint8_t* out,
+                                  int flags) {
+    if (!ctx) return SGPU_EINVAL;
+    if (ndesc == 0) return SGPU_OK;
+    if (!d || !out) return ctx->fail(SGPU_EINVAL, "bad quantize arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (flags & SGPU_INPUT_DEVICE) {
+        HIPCHK(ctx, sgk::launch_quantize_desc(d, ndesc, out, nullptr, nullptr, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        return SGPU_OK;
+    }
+    ALLOCCHK(ctx, ctx->q_in.ensure(ndesc * 128 * sizeof(float)));
+    ALLOCCHK(ctx, ctx->q_out.ensure(ndesc * 128));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->q_in.p, d, ndesc * 128 * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, sgk::launch_quantize_desc(ctx->q_in.as<float>(), ndesc, ctx->q_out.as<uint8_t>(),
+                                          nullptr, nullptr, st));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->q_out.p, ndesc * 128, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return SGPU_OK;
+}
+
+// The last extract's descriptors as u8 (and, for the matcher, s8 and row sums): one
+// k_quantize_desc launch over the batch's float descriptors on first request, kept until the
+// batch or the options change (f_ready).
+static int feature_u8(sgpu_ctx* ctx) {
+    if (ctx->batch <= 0 || ctx->img_off.empty())
+        return ctx->fail(SGPU_EINVAL, "no extracted batch to quantise");
+    if (!ctx->opt.descriptors) return ctx->fail(SGPU_EINVAL, "descriptors disabled (-sd)");
+    if (ctx->f_ready) return SGPU_OK;
+    const float* dsc = nullptr;
+    const int rc = sgpu_device_features(ctx, nullptr, &dsc, nullptr);   // (gathers a multi-part batch)
+    if (rc != SGPU_OK) return rc;
+    const size_t total = (size_t)ctx->img_off[ctx->batch];
+    ALLOCCHK(ctx, ctx->f_u8.ensure(std::max<size_t>(total, 1) * 128));
+    ALLOCCHK(ctx, ctx->f_s8.ensure(std::max<size_t>(total, 1) * 128));
+    ALLOCCHK(ctx, ctx->f_sums.ensure(std::max<size_t>(total, 1) * sizeof(int)));
+    if (total > 0) {
+        if (!dsc) return ctx->fail(SGPU_EINVAL, "the batch has no descriptors");
+        HIPCHK(ctx, sgk::launch_quantize_desc(dsc, total, ctx->f_u8.as<uint8_t>(),
+                                              ctx->f_s8.as<uint8_t>(), ctx->f_sums.as<int>(),
+                                              ctx->stream));
+    }
+    ctx->f_ready = true;
+    return SGPU_OK;
+}
+
+int sgpu_feature_descriptors_u8(sgpu_ctx* ctx, const uint8_t** desc_u8) {
+    if (!ctx || !desc_u8) return SGPU_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = feature_u8(ctx);
+    if (rc != SGPU_OK) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // readable from any stream of the caller
+    *desc_u8 = ctx->f_u8.as<uint8_t>();
+    return SGPU_OK;
+}
+
+int sgpu_copy_features_u8(sgpu_ctx* ctx, int image, uint8_t* desc) {
+    if (!ctx) return SGPU_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = feature_u8(ctx);
+    if (rc != SGPU_OK) return rc;
+    if (image < 0 || image >= ctx->batch) return ctx->fail(SGPU_EINVAL, "no such image");
+    const int64_t a = ctx->img_off[image], nf = ctx->img_off[image + 1] - a;
+    if (nf <= 0) return SGPU_OK;
+    if (!desc) return ctx->fail(SGPU_EINVAL, "null output");
+    HIPCHK(ctx, hipMemcpyAsync(desc, ctx->f_u8.as<uint8_t>() + a * 128, (size_t)nf * 128,
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return SGPU_OK;
+}
+
+// The grouped pair matcher over device-resident sets: u8 = the sets' descriptors, s8 / sums =
+// their matcher forms when the caller has them (sgpu_match_images), else derived here in one
+// launch.  One table upload, six launches, two device->host copies and two
+// synchronisations, whatever npairs is.
+static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8, const int* sums,
+                            const int64_t* off, int nsets, const int* set_pairs, int npairs,
+                            float distmax, float ratiomax, int mbm, int max_match, int* out_pairs,
+                            int64_t cap, int* out_counts, bool timing_started = false) {
+    hipStream_t st = ctx->stream;
+    sgplan::Plan& plan = ctx->b_hplan;
+    const int prc = sgplan::build_plan(off, nsets, set_pairs, npairs, mbm != 0, max_match, plan);
+    if (prc == sgplan::kPlanBadArgument)
+        return ctx->fail(SGPU_EINVAL, "bad set offsets or pair indices");
+    if (prc != sgplan::kPlanOk) return ctx->fail(SGPU_ERANGE, "match batch too large");
+    if (npairs == 0) return 0;
+    if (!out_counts) return ctx->fail(SGPU_EINVAL, "null out_counts");
+    if (cap < 0) cap = 0;
+    if (cap > 0 && !out_pairs) return ctx->fail(SGPU_EINVAL, "null out_pairs");
+    const int64_t total_rows = off[nsets];
+    if (plan.items.empty()) {   // every pair has an empty set
+        for (int p = 0; p < npairs; p++) out_counts[p] = 0;
+        ctx->timing[T_MATCH] = 0.f;
+        return 0;
+    }
+    if (!u8) return ctx->fail(SGPU_EINVAL, "null descriptors");
+    if (!ctx->dist_ready) {
+        // the same expression as RowMatch_Kernel (ProgramCU.cu:1838), evaluated on the host
+        std::vector<float> t(sgk::kDistTable);
+        for (int v = 0; v < sgk::kDistTable; v++)
+            t[v] = (float)std::acos(std::min((double)(v * 0.000003814697265625f), 1.0));
+        ALLOCCHK(ctx, ctx->m_dist.ensure(t.size() * sizeof(float)));
+        HIPCHK(ctx, hipMemcpy(ctx->m_dist.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+        ctx->dist_ready = true;
+    }
+    // the tables in one buffer, one upload: [items][sides][finish panels][pairs]
+    const size_t b_items = plan.items.size() * sizeof(sgplan::Item);
+    const size_t b_sides = plan.sides.size() * sizeof(sgplan::Side);
+    const size_t b_fp = plan.fpanels.size() * sizeof(sgplan::FinishPanel);
+    const size_t b_pairs = plan.pairs.size() * sizeof(sgplan::PairRec);
+    ctx->b_tables.resize(b_items + b_sides + b_fp + b_pairs);
+    unsigned char* tb = ctx->b_tables.data();
+    memcpy(tb, plan.items.data(), b_items);
+    memcpy(tb + b_items, plan.sides.data(), b_sides);
+    memcpy(tb + b_items + b_sides, plan.fpanels.data(), b_fp);
+    memcpy(tb + b_items + b_sides + b_fp, plan.pairs.data(), b_pairs);
+    const int64_t out_rows = std::min<int64_t>(cap, plan.out_bound);
+    ALLOCCHK(ctx, ctx->b_plan.ensure(ctx->b_tables.size()));
+    ALLOCCHK(ctx, ctx->b_part.ensure((size_t)plan.part_total * sizeof(sgk::Top2)));
+    ALLOCCHK(ctx, ctx->b_dec.ensure((size_t)plan.dec_total * sizeof(int)));
+    // [offsets npairs + 1 (64-bit)][counts npairs]
+    ALLOCCHK(ctx, ctx->b_cnt.ensure((size_t)(npairs + 1) * sizeof(long long) + (size_t)npairs * sizeof(int)));
+    ALLOCCHK(ctx, ctx->b_out.ensure((size_t)std::max<int64_t>(out_rows, 1) * 2 * sizeof(int)));
+    if (!s8 || !sums) {
+        ALLOCCHK(ctx, ctx->b_s8.ensure((size_t)total_rows * 128));
+        ALLOCCHK(ctx, ctx->b_sums.ensure((size_t)total_rows * sizeof(int)));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->b_plan.p, tb, ctx->b_tables.size(), hipMemcpyHostToDevice, st));
+    const unsigned char* dt = ctx->b_plan.as<unsigned char>();
+    const auto* d_items = reinterpret_cast<const sgplan::Item*>(dt);
+    const auto* d_sides = reinterpret_cast<const sgplan::Side*>(dt + b_items);
+    const auto* d_fp = reinterpret_cast<const sgplan::FinishPanel*>(dt + b_items + b_sides);
+    const auto* d_pairs = reinterpret_cast<const sgplan::PairRec*>(dt + b_items + b_sides + b_fp);
+    long long* d_offs = ctx->b_cnt.as<long long>();
+    int* d_counts = reinterpret_cast<int*>(d_offs + npairs + 1);
+    if (!timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    if (!s8 || !sums) {
+        HIPCHK(ctx, sgk::launch_prep_set(u8, (int)total_rows, ctx->b_s8.as<uint8_t>(),
+                                         ctx->b_sums.as<int>(), 128, 0, nullptr, 0, st));
+        s8 = ctx->b_s8.as<uint8_t>();
+        sums = ctx->b_sums.as<int>();
+    }
+    HIPCHK(ctx, sgk::launch_match_pairs(s8, d_items, (int)plan.items.size(),
+                                        ctx->b_part.as<sgk::Top2>(), st));
+    HIPCHK(ctx, sgk::launch_match_pairs_finish(ctx->b_part.as<sgk::Top2>(), d_sides, d_fp,
+                                               (int)plan.fpanels.size(), sums,
+                                               ctx->m_dist.as<float>(), distmax, ratiomax,
+                                               ctx->b_dec.as<int>(), st));
+    HIPCHK(ctx, sgk::launch_match_pairs_compact(ctx->b_dec.as<int>(), d_pairs, npairs, max_match,
+                                                out_rows, d_counts, d_offs, ctx->b_out.as<int>(), st));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[2], st));
+    HIPCHK(ctx, hipMemcpyAsync(out_counts, d_counts, (size_t)npairs * sizeof(int),
+                               hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&ctx->timing[T_MATCH], ctx->ev[1], ctx->ev[2]);
+    // the pairs that fit form a prefix (the offsets only grow): copy their matches
+    int64_t total = 0, fit = 0;
+    bool fits = true;
+    for (int p = 0; p < npairs; p++) {
+        total += out_counts[p];
+        fits = fits && total <= cap;
+        if (fits) fit = total;
+    }
+    if (fit > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(out_pairs, ctx->b_out.p, (size_t)fit * 2 * sizeof(int),
+                                   hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+    }
+    if (total > cap) return ctx->fail(SGPU_ERANGE, "matches exceed cap (counts are complete)");
+    if (total > INT_MAX) return ctx->fail(SGPU_ERANGE, "match total exceeds the return type");
+    return (int)total;
+}
+
+int sgpu_match_batch(sgpu_ctx* ctx, const uint8_t* desc, const int64_t* set_offsets, int nsets,
+                     const int* set_pairs, int npairs, float distmax, float ratiomax,
+                     int mutual_best_match, int max_match, int* out_pairs, int64_t cap,
+                     int* out_counts, int flags) {
+    if (!ctx) return SGPU_EINVAL;
+    if (nsets < 0 || npairs < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad match batch arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint8_t* u8 = desc;
+    if (!(flags & SGPU_INPUT_DEVICE) && npairs > 0) {
+        // validated offsets before any size is taken from them
+        sgplan::Plan probe;
+        if (sgplan::build_plan(set_offsets, nsets, nullptr, 0, false, 0, probe) != sgplan::kPlanOk)
+            return ctx->fail(SGPU_EINVAL, "bad set offsets");
+        const int64_t total_rows = set_offsets[nsets];
+        if (total_rows > 0) {
+            if (!desc) return ctx->fail(SGPU_EINVAL, "null descriptors");
+            ALLOCCHK(ctx, ctx->b_desc.ensure((size_t)total_rows * 128));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->b_desc.p, desc, (size_t)total_rows * 128,
+                                       hipMemcpyHostToDevice, ctx->stream));
+            u8 = ctx->b_desc.as<uint8_t>();
+        }
+    }
+    return match_batch_impl(ctx, u8, nullptr, nullptr, set_offsets, nsets, set_pairs, npairs, distmax,
+                            ratiomax, mutual_best_match, max_match, out_pairs, cap, out_counts);
+}
+
+int sgpu_match_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, float distmax,
+                      float ratiomax, int mutual_best_match, int max_match, int* out_pairs,
+                      int64_t cap, int* out_counts) {
+    if (!ctx) return SGPU_EINVAL;
+    if (npairs < 0) return ctx->fail(SGPU_EINVAL, "bad match arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // a quantisation this call has to make counts into its device time (times[8]); it is queued
+    // on the matcher's stream, with no wait in between
+    const bool quantises = !ctx->f_ready;
+    if (quantises) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    const int rc = feature_u8(ctx);
+    if (rc != SGPU_OK) return rc;
+    return match_batch_impl(ctx, ctx->f_u8.as<uint8_t>(), ctx->f_s8.as<uint8_t>(),
+                            ctx->f_sums.as<int>(), ctx->img_off.data(), ctx->batch, image_pairs,
+                            npairs, distmax, ratiomax, mutual_best_match, max_match, out_pairs, cap,
+                            out_counts, quantises);
 }
 
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n) {

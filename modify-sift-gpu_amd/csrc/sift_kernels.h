@@ -340,3 +340,36 @@ hipError_t launch_match_finish(const Top2* part, int n, int chunks, const int* r
                                int nB = 0, ColumnList cl = ColumnList{});
 
 }  // namespace sgk
+
+// ---- grouped pair matcher and device quantiser (sift_match_batch.hip) ----
+// the host planner's tables (sift_match_plan.h), uploaded once per call
+namespace sgplan {
+struct Item;
+struct Side;
+struct FinishPanel;
+struct PairRec;
+}  // namespace sgplan
+
+namespace sgk {
+// float descriptors d [n][128] -> u8 by the rule of sgpu_quantize_descriptors, and in the same
+// pass the matcher's forms of the set: s8 = u8 xor 0x80 and sums[i] = 128 * sum_k u8[i][k].  Any of
+// the outputs may be null.
+hipError_t launch_quantize_desc(const float* d, size_t n, uint8_t* u8, uint8_t* s8, int* sums,
+                                hipStream_t stream);
+// One workgroup per work item (pair, direction, panel of A, column chunk of B) over the s8 buffer
+// of all sets: part[item.part_base + row] = the row's top-2 over the chunk (dot - row term).
+hipError_t launch_match_pairs(const uint8_t* s8, const sgplan::Item* items, int nitems, Top2* part,
+                              hipStream_t stream);
+// One workgroup per (side, panel): merge the side's chunks, add the row term sums[a_off + row],
+// apply distmax / ratiomax -> dec[side.dec_off + row] = matched column of B or -1.
+hipError_t launch_match_pairs_finish(const Top2* part, const sgplan::Side* sides,
+                                     const sgplan::FinishPanel* fpanels, int nfpanels,
+                                     const int* sums, const float* dist, float distmax,
+                                     float ratiomax, int* dec, hipStream_t stream);
+// Mutual check and ordered compaction, three launches: counts[p] = min(matches of pair p,
+// max_match), offs[0 .. npairs] = their exclusive scan, out[offs[p] ..) = pair p's {i, j} in
+// ascending i for every pair with offs[p] + counts[p] <= cap.
+hipError_t launch_match_pairs_compact(const int* dec, const sgplan::PairRec* pairs, int npairs,
+                                      int max_match, long long cap, int* counts, long long* offs,
+                                      int* out, hipStream_t stream);
+}  // namespace sgk

@@ -34,6 +34,8 @@ C_API = [
     "sgpu_extract_stream", "sgpu_host_alloc", "sgpu_host_free", "sgpu_reserve",
     "sgpu_debug_alloc_count", "sgpu_last_pyramid_launches", "sgpu_set_stage_timing",
     "sgpu_set_host_output", "sgpu_debug_set_schedule", "sgpu_debug_set_match_prune",
+    "sgpu_quantize_descriptors_gpu", "sgpu_feature_descriptors_u8", "sgpu_copy_features_u8",
+    "sgpu_match_batch", "sgpu_match_images",
 ]
 
 _LIB = None
@@ -102,6 +104,13 @@ def lib():
         L.sgpu_host_alloc.argtypes = [c.c_size_t]
         L.sgpu_host_alloc.restype = vp
         L.sgpu_host_free.argtypes = [vp]
+        L.sgpu_quantize_descriptors_gpu.argtypes = [vp, vp, c.c_size_t, vp, c.c_int]
+        L.sgpu_feature_descriptors_u8.argtypes = [vp, P(vp)]
+        L.sgpu_copy_features_u8.argtypes = [vp, c.c_int, vp]
+        L.sgpu_match_batch.argtypes = [vp, vp, vp, c.c_int, vp, c.c_int, c.c_float, c.c_float,
+                                       c.c_int, c.c_int, vp, c.c_int64, vp, c.c_int]
+        L.sgpu_match_images.argtypes = [vp, vp, c.c_int, c.c_float, c.c_float, c.c_int, c.c_int,
+                                        vp, c.c_int64, vp]
         _LIB = L
     return _LIB
 
@@ -166,6 +175,29 @@ def quantize(desc: np.ndarray) -> np.ndarray:
     out = np.empty(d.shape, np.uint8)
     lib().sgpu_quantize_descriptors(d.ctypes.data, d.size, out.ctypes.data)
     return out
+
+
+def quantize_gpu(desc: np.ndarray, ctx: "SiftContext | None" = None) -> np.ndarray:
+    """quantize() on the device (sgpu_quantize_descriptors_gpu, host pointers): the same bytes.
+    Without a context a temporary one on device 0 is used."""
+    own = ctx is None
+    if own:
+        ctx = SiftContext(0)
+    try:
+        return ctx.quantize_gpu(desc)
+    finally:
+        if own:
+            ctx.close()
+
+
+class MatchOverflow(RuntimeError):
+    """match_batch / match_images found more matches than `cap` (SGPU_ERANGE): .counts holds
+    every pair's complete count, .matches the leading pairs that fit."""
+
+    def __init__(self, counts, matches):
+        super().__init__(f"{int(counts.sum())} matches exceed cap")
+        self.counts = counts
+        self.matches = matches
 
 
 class SiftContext:
@@ -417,6 +449,76 @@ class SiftContext:
         if m < 0:
             self._check(m, "sgpu_match")
         return out[:m]
+
+    def quantize_gpu(self, desc: np.ndarray) -> np.ndarray:
+        """Float descriptors [n, 128] -> u8 on the device, byte for byte sgpu.quantize()."""
+        d = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
+        out = np.empty(d.shape, np.uint8)
+        self._check(lib().sgpu_quantize_descriptors_gpu(self._ctx, d.ctypes.data, d.shape[0],
+                                                        out.ctypes.data, SGPU_INPUT_HOST),
+                    "sgpu_quantize_descriptors_gpu")
+        return out
+
+    def features_u8(self, image: int = 0) -> np.ndarray:
+        """Image `image`'s descriptors of the last extract as u8 [n, 128], quantised on the
+        device (sgpu_copy_features_u8)."""
+        out = np.zeros((self.count(image), 128), np.uint8)
+        self._check(lib().sgpu_copy_features_u8(self._ctx, image, out.ctypes.data if len(out) else None),
+                    "sgpu_copy_features_u8")
+        return out
+
+    def _pair_results(self, call, pairs, sizes, max_match, cap):
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        npairs = len(pr)
+        if max_match is None:
+            max_match = int(max(sizes)) if len(sizes) else 0
+        if cap is None:
+            ok = (pr >= 0).all() and (pr < len(sizes)).all()
+            cap = int(sum(min(int(sizes[a]), max_match) for a in pr[:, 0])) if ok and max_match > 0 else 0
+        out = np.zeros((max(int(cap), 1), 2), np.int32)
+        counts = np.zeros(max(npairs, 1), np.int32)
+        rc = call(pr, npairs, int(max_match), out, int(cap), counts)
+        counts = counts[:npairs]
+        if rc < 0 and rc != SGPU_ERANGE:
+            self._check(rc, "match batch")
+        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        res = [out[offs[p]:offs[p + 1]].copy() for p in range(npairs) if offs[p + 1] <= cap]
+        if rc == SGPU_ERANGE:
+            raise MatchOverflow(counts.copy(), res)
+        return res
+
+    def match_batch(self, desc_u8: np.ndarray, offsets, pairs, distmax=0.7, ratiomax=0.8, mbm=1,
+                    max_match=None, cap=None):
+        """Many set pairs of one u8 descriptor buffer in one call (sgpu_match_batch): set s =
+        rows [offsets[s], offsets[s + 1]), pairs [(a, b), ...].  Returns one [m, 2] int32 array
+        per pair, each what match(set a, set b) returns.  max_match: per pair (default: no
+        limit); cap: total capacity (default: enough for every pair); more matches than cap raise
+        MatchOverflow."""
+        d = np.ascontiguousarray(desc_u8, np.uint8).reshape(-1, 128)
+        off = np.ascontiguousarray(offsets, np.int64)
+        nsets = len(off) - 1
+        if nsets < 0 or (nsets >= 0 and len(off) and off[-1] > len(d)):
+            raise ValueError("offsets do not fit the descriptor buffer")
+        sizes = np.diff(off)
+
+        def call(pr, npairs, mm, out, cp, counts):
+            return lib().sgpu_match_batch(self._ctx, d.ctypes.data if len(d) else None,
+                                          off.ctypes.data, nsets, pr.ctypes.data if npairs else None,
+                                          npairs, distmax, ratiomax, mbm, mm, out.ctypes.data, cp,
+                                          counts.ctypes.data, SGPU_INPUT_HOST)
+        return self._pair_results(call, pairs, sizes, max_match, cap)
+
+    def match_images(self, pairs, distmax=0.7, ratiomax=0.8, mbm=1, max_match=None, cap=None):
+        """Image pairs [(a, b), ...] of the last extract matched on the device
+        (sgpu_match_images): the descriptors are quantised in HBM and never leave it.  Returns
+        one [m, 2] int32 array per pair."""
+        sizes = np.array([self.count(i) for i in range(self.batch)], np.int64)
+
+        def call(pr, npairs, mm, out, cp, counts):
+            return lib().sgpu_match_images(self._ctx, pr.ctypes.data if npairs else None, npairs,
+                                           distmax, ratiomax, mbm, mm, out.ctypes.data, cp,
+                                           counts.ctypes.data)
+        return self._pair_results(call, pairs, sizes, max_match, cap)
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
