@@ -385,6 +385,12 @@ int sgpu_debug_set_schedule(sgpu_ctx* ctx, int trio, int pairs);
  * shipped default; SGPU_MATCH_PRUNE=off at context creation turns it off): the same pairs
  * (DESIGN.md 4.8), a test / A-B hook. */
 int sgpu_debug_set_match_prune(sgpu_ctx* ctx, int on);
+/* The plan of the last sgpu_match_batch / sgpu_match_images call, read-only:
+ * out[0] = work items, out[1] = sides, out[2] = the most 128-column tiles of any item,
+ * ceil((c_end - c_begin) / 128), out[3] = the most column chunks of any side (all 0 for a call
+ * with no pair of two non-empty sets).  SGPU_EINVAL before the first such call and after one whose
+ * offsets or pair indices were rejected.  Tests use it to prove which plan regime they ran in. */
+int sgpu_debug_match_plan_stats(const sgpu_ctx* ctx, long long out[4]);
 /* Octave geometry of the last extract: n_octaves, and (w, h, wa) per octave. */
 int sgpu_debug_geometry(const sgpu_ctx* ctx, int* n_octaves, int* dims /* 3*max */, int max);
 /* Gaussian level (image, octave, level 0..level_num-1) as wa*h floats. */

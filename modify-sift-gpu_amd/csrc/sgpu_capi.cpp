@@ -232,6 +232,7 @@ struct sgpu_ctx {
     // the planner's tables, chunk partials, decisions, [counts npairs][offsets npairs + 1], pairs
     DevBuf b_desc, b_s8, b_sums, b_plan, b_part, b_dec, b_cnt, b_out;
     sgplan::Plan b_hplan;
+    bool b_planned = false;                // b_hplan is a call's plan (sgpu_debug_match_plan_stats)
     std::vector<unsigned char> b_tables;   // the tables as uploaded (alive until the call's sync)
     // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
     // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
@@ -2317,6 +2318,7 @@ static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8,
     hipStream_t st = ctx->stream;
     sgplan::Plan& plan = ctx->b_hplan;
     const int prc = sgplan::build_plan(off, nsets, set_pairs, npairs, mbm != 0, max_match, plan);
+    ctx->b_planned = prc == sgplan::kPlanOk;
     if (prc == sgplan::kPlanBadArgument)
         return ctx->fail(SGPU_EINVAL, "bad set offsets or pair indices");
     if (prc != sgplan::kPlanOk) return ctx->fail(SGPU_ERANGE, "match batch too large");
@@ -2467,6 +2469,20 @@ int sgpu_debug_set_flags(sgpu_ctx* ctx, int flags) {
 int sgpu_debug_set_match_prune(sgpu_ctx* ctx, int on) {
     if (!ctx) return SGPU_EINVAL;
     ctx->match_prune = on != 0;
+    return SGPU_OK;
+}
+
+int sgpu_debug_match_plan_stats(const sgpu_ctx* ctx, long long out[4]) {
+    if (!ctx || !out || !ctx->b_planned) return SGPU_EINVAL;
+    const sgplan::Plan& plan = ctx->b_hplan;
+    long long tiles = 0, chunks = 0;
+    for (const sgplan::Item& it : plan.items)
+        tiles = std::max<long long>(tiles, (it.c_end - it.c_begin + sgplan::kTileCols - 1) / sgplan::kTileCols);
+    for (const sgplan::Side& sd : plan.sides) chunks = std::max<long long>(chunks, sd.chunks);
+    out[0] = (long long)plan.items.size();
+    out[1] = (long long)plan.sides.size();
+    out[2] = tiles;
+    out[3] = chunks;
     return SGPU_OK;
 }
 

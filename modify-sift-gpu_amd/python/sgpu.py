@@ -35,7 +35,7 @@ C_API = [
     "sgpu_debug_alloc_count", "sgpu_last_pyramid_launches", "sgpu_set_stage_timing",
     "sgpu_set_host_output", "sgpu_debug_set_schedule", "sgpu_debug_set_match_prune",
     "sgpu_quantize_descriptors_gpu", "sgpu_feature_descriptors_u8", "sgpu_copy_features_u8",
-    "sgpu_match_batch", "sgpu_match_images",
+    "sgpu_match_batch", "sgpu_match_images", "sgpu_debug_match_plan_stats",
 ]
 
 _LIB = None
@@ -111,6 +111,7 @@ def lib():
                                        c.c_int, c.c_int, vp, c.c_int64, vp, c.c_int]
         L.sgpu_match_images.argtypes = [vp, vp, c.c_int, c.c_float, c.c_float, c.c_int, c.c_int,
                                         vp, c.c_int64, vp]
+        L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -602,6 +603,15 @@ class SiftContext:
         column's decision (sgpu_debug_set_match_prune; on = shipped): the same pairs."""
         self._check(lib().sgpu_debug_set_match_prune(self._ctx, int(bool(on))),
                     "sgpu_debug_set_match_prune")
+
+    def match_plan_stats(self):
+        """The last match_batch / match_images call's plan (sgpu_debug_match_plan_stats): dict of
+        items, sides, max_tiles (most 128-column tiles of an item) and max_chunks (most column
+        chunks of a side)."""
+        out = np.zeros(4, np.int64)
+        self._check(lib().sgpu_debug_match_plan_stats(self._ctx, out.ctypes.data),
+                    "sgpu_debug_match_plan_stats")
+        return dict(zip(["items", "sides", "max_tiles", "max_chunks"], out.tolist()))
 
     @contextlib.contextmanager
     def exact_descriptors(self):

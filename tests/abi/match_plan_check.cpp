@@ -132,6 +132,16 @@ static void check(const char* name, const std::vector<int>& sizes,
     REQUIRE(plan.fpanels.size() == expect_fp);
 }
 
+static void build_for(const std::vector<int>& sizes, const std::vector<std::pair<int, int>>& pairs,
+                      bool mutual, int max_match, Plan& plan) {
+    std::vector<int64_t> off(sizes.size() + 1, 0);
+    for (size_t s = 0; s < sizes.size(); s++) off[s + 1] = off[s] + sizes[s];
+    std::vector<int> flat;
+    for (auto& p : pairs) { flat.push_back(p.first); flat.push_back(p.second); }
+    REQUIRE(build_plan(off.data(), (int)sizes.size(), flat.data(), (int)pairs.size(), mutual,
+                       max_match, plan) == kPlanOk);
+}
+
 int main() {
     // the sets and pair list of the GPU size test
     const std::vector<int> sizes = {0, 1, 127, 128, 129, 257, 700, 3000};
@@ -159,6 +169,51 @@ int main() {
         Plan plan;
         REQUIRE(build_plan(off, 2, pr, 1, true, 3000, plan) == kPlanOk);
         REQUIRE((int)plan.items.size() >= kCUs);
+    }
+    // Filler pairs (tests/test_gpu_match_batch.py): thousands of one-row mutual pairs add two
+    // panels each, so the real pairs of the same call get the panel-limited plans (1, 2 or 3
+    // chunks per side) that a shard's pair list gets.
+    {
+        // 3000 x 9000 with 2100 fillers: one chunk per side, 71 and 24 tiles
+        std::vector<int> fsizes = {3000, 9000, 1, 1};
+        std::vector<std::pair<int, int>> fpairs = {{0, 1}};
+        for (int k = 0; k < 2100; k++) fpairs.push_back({2, 3});
+        check("filler ties", fsizes, fpairs, true, 3000);
+        g_case = "filler ties tiles";
+        Plan plan;
+        build_for(fsizes, fpairs, true, 3000, plan);
+        int tiles[2] = {0, 0}, items[2] = {0, 0};
+        for (const Side& sd : plan.sides)
+            if (sd.pair == 0) REQUIRE(sd.chunks == 1);
+        for (const Item& it : plan.items)
+            if (it.pair == 0) {
+                REQUIRE(it.c_begin == 0);
+                tiles[it.dir] = std::max(tiles[it.dir], (it.c_end - it.c_begin + kTileCols - 1) / kTileCols);
+                items[it.dir]++;
+            }
+        REQUIRE(tiles[0] == 71 && tiles[1] == 24);
+        REQUIRE(items[0] == 24 && items[1] == 71);   // one item per panel
+    }
+    {
+        // the GPU size test's sets and pairs under 1010 fillers: at most 2 chunks per side, and
+        // some side has 2
+        std::vector<int> fsizes = {0, 1, 127, 128, 129, 257, 385, 513, 700, 897, 3000, 1, 1};
+        std::vector<std::pair<int, int>> fpairs;
+        for (int s = 0; s + 1 < 11; s++) fpairs.push_back({s, s + 1});
+        fpairs.insert(fpairs.end(), {{5, 5}, {7, 4}, {4, 7}, {9, 10}, {8, 6}, {6, 8}, {0, 4}, {4, 0}, {0, 0}});
+        const size_t real = fpairs.size();
+        for (int k = 0; k < 1010; k++) fpairs.push_back({11, 12});
+        for (int mutual = 0; mutual < 2; mutual++) check("filler sizes", fsizes, fpairs, mutual != 0, 3000);
+        g_case = "filler sizes chunks";
+        Plan plan;
+        build_for(fsizes, fpairs, true, 3000, plan);
+        int most = 0;
+        for (const Side& sd : plan.sides) {
+            REQUIRE(sd.chunks <= 2);
+            if (sd.pair >= (int)real) REQUIRE(sd.chunks == 1);
+            most = std::max(most, sd.chunks);
+        }
+        REQUIRE(most == 2);
     }
     check("no pairs", sizes, {}, true, 10);
     check("all empty", {0, 0}, {{0, 1}, {1, 0}}, true, 10);
