@@ -379,6 +379,15 @@ int sgpu_debug_set_flags(sgpu_ctx* ctx, int flags);
 #define SGPU_PAIRS_FRONT 0
 #define SGPU_PAIRS_END 1
 int sgpu_debug_set_schedule(sgpu_ctx* ctx, int trio, int pairs);
+/* Strip geometry of the paired-level launches (k_gauss_duo), a test / A-B hook --
+ * the levels are the same bits in every form.  RULE (shipped): a workgroup's four waves share one
+ * strip of 480 columns where that issues fewer lane-columns than a strip of 96 columns per wave
+ * (1920, 960 and 480 columns, not 240; levels of at most 1920 columns) and measured faster; WAVE: a strip per wave on
+ * every level; COOP: the shared strip wherever it is compiled, at any width. */
+#define SGPU_DUO_STRIPS_RULE 0
+#define SGPU_DUO_STRIPS_WAVE 1
+#define SGPU_DUO_STRIPS_COOP 2
+int sgpu_debug_set_duo_strips(sgpu_ctx* ctx, int mode);
 /* Plain mutual matching (ratiomax <= 1) decides the listed columns over the rows of set 1 that can
  * change a decision -- those with some dot at or above the smallest second value that fails the
  * ratio test against the weakest passing row maximum -- instead of all of set 1 (on != 0, the

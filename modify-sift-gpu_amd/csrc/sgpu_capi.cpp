@@ -181,6 +181,8 @@ struct sgpu_ctx {
                                            // always; sgpu_debug_set_schedule)
     int duo_plan = SGK_DUO_PLAN;           // SGPU_PAIRS_END: pairs from the octave's end
                                            // (SGPU_DUO_PLAN=end), SGPU_PAIRS_FRONT: from its front
+    int duo_strips = SGPU_DUO_STRIPS_RULE; // strip geometry of the paired-level launches
+                                           // (sgpu_debug_set_duo_strips)
     size_t wide_desc_max = SGK_WIDE_DESC_MAX;   // feature counts (of the previous call) up to which
                                            // descriptors run a workgroup per feature
                                            // (SGPU_WIDE_DESC_MAX)
@@ -971,7 +973,7 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
                     pt.gauss_launches++;
                 } else if (duo_second[i] && e.o * kds + e.k == slot) {   // the pair ends in this slot
                     HIPCHK(ctx, sgk::launch_gauss_duo(ops[i - 1].op, e.op, st, wave_rows,
-                                                      ctx->duo_trash.as<float>()));
+                                                      ctx->duo_trash.as<float>(), ctx->duo_strips));
                     pt.gauss_launches++;
                 } else if (!in_trio[i] && duo_next[i] < 0 && !duo_second[i] && e.o * kds + e.k == slot) {
                     in_slot[m++] = &e.op;
@@ -2483,6 +2485,14 @@ int sgpu_debug_match_plan_stats(const sgpu_ctx* ctx, long long out[4]) {
     out[1] = (long long)plan.sides.size();
     out[2] = tiles;
     out[3] = chunks;
+    return SGPU_OK;
+}
+
+static_assert(SGPU_DUO_STRIPS_RULE == sgk::kDuoStripsRule && SGPU_DUO_STRIPS_WAVE == sgk::kDuoStripsWave &&
+              SGPU_DUO_STRIPS_COOP == sgk::kDuoStripsCoop, "sgpu.h and sift_kernels.h agree");
+int sgpu_debug_set_duo_strips(sgpu_ctx* ctx, int mode) {
+    if (!ctx || mode < SGPU_DUO_STRIPS_RULE || mode > SGPU_DUO_STRIPS_COOP) return SGPU_EINVAL;
+    ctx->duo_strips = mode;
     return SGPU_OK;
 }
 

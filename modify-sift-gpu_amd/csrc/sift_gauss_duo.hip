@@ -8,8 +8,15 @@
 // vertical passes are register-resident ("push" form), so a wave's LDS is its input rows and
 // one mid row pair:
 //
-//   * a wave owns SW = 128 - 2 RB output columns of both levels (RB = FWB / 2) and walks a band
-//     of rows top to bottom, two rows (one row pair) per step;
+//   * a wave computes a window of 128 columns of level k+1 ("mid" columns, two per lane) and
+//     walks a band of rows top to bottom, two rows (one row pair) per step.  Per-wave strips: the
+//     wave works alone and owns the SW = (128 - 2 MOFF) rounded down to 32 = 96 columns of both
+//     levels that its own window covers with RB = FWB / 2 halo columns on each side (MOFF = RB
+//     rounded up to even).  Cooperative strips (COOP, DESIGN.md 4.10, sift_gauss_coop_plan.h):
+//     the four waves of a workgroup tile one 512-column window without overlap and own
+//     SWG = 480 columns, stage B of a wave reading its halo columns from the neighbouring
+//     waves' mid blocks in LDS -- 4 wave-steps per 480 columns instead of 5, at the price of
+//     one workgroup barrier per step (lgkmcnt(0) + s_barrier: the DMA ring is not drained);
 //   * stage A: the input row pair (128 + 2 RA columns, clamped to the image) arrives in LDS by
 //     LDS-DMA NIN - 1 steps ahead of its use -- no staging registers.  Pairs of < 40 taps
 //     (SGK_DUO_X4): two global_load_lds_dwordx4 (16 B per lane) into a row-major slot, H1 (lane
@@ -31,7 +38,10 @@
 //   * clamp-to-edge: stage A's rows and columns are clamped in the DMA addresses; stage B's rows
 //     above 0 / below H-1 read two extra LDS pairs, (mid 0, mid 0) -- computed by a short
 //     prologue in the top band -- and (mid H-1, mid H-1); stage B's columns outside the image
-//     take the edge mid column's value by v_readlane in the two edge strips.
+//     take the edge mid column's value by v_readlane in the two edge strips (cooperative: in
+//     the waves that hold column 0 and column W-1; the latter also writes that value into the
+//     first columns of the next wave's block where the clamped columns run past its own, and a
+//     wave wholly outside the image only keeps the barriers).
 //
 // Every VMEM instruction of a step is issued unconditionally (rows outside the band store to a
 // per-wave scratch area), so the count of memory operations younger than a step's DMA is a
@@ -44,6 +54,7 @@
 #include <cstring>
 #include <utility>
 
+#include "sift_gauss_coop_plan.h"
 #include "sift_gauss_ring.h"
 #include "sift_kernels.h"
 
@@ -65,7 +76,9 @@ constexpr bool kDuoInterleave = SGK_DUO_INTERLEAVE != 0;
 // timing experiments only (wrong levels, tests/diag): 1 = DMA lanes row-contiguous (lanes 0-31 row
 // 2p, 32-63 row 2p+1), 2 = no H / V arithmetic (one LDS read per pass), 3 = the row pair as two
 // 16-B-per-lane DMAs (global_load_lds_dwordx4, 128 lane addresses instead of 320), 4 = the same
-// with the second on 8 lanes (72 lane addresses), 0 = the kernel
+// with the second on 8 lanes (72 lane addresses), 5 = the per-wave kernel (right levels) plus the
+// cooperative form's one workgroup barrier per step (what the barrier alone costs, DESIGN.md
+// 4.10), 0 = the kernel
 #ifndef SGK_DUO_EXP
 #define SGK_DUO_EXP 0
 #endif
@@ -75,8 +88,20 @@ constexpr bool kDuoInterleave = SGK_DUO_INTERLEAVE != 0;
 #ifndef SGK_DUO_X4
 #define SGK_DUO_X4 1
 #endif
-constexpr int kDuoWaves = 4;      // waves per workgroup (each wave works alone: no barriers)
-constexpr int kMidSlot = 256;     // floats of one mid row pair: 128 columns x (row, row + 1)
+constexpr int kDuoWaves = 4;      // waves per workgroup (per-wave form: each works alone, no barriers)
+constexpr int kMidSlot = 256;     // floats of one wave's mid row pair: 128 columns x (row, row + 1)
+static_assert(kDuoWaves == coop::kWaves && 2 * coop::kWaveCols == kMidSlot, "cooperative geometry");
+
+// the cooperative form's workgroup barrier: this wave's LDS writes and reads have completed
+// (lgkmcnt(0)); not __syncthreads(), whose vmcnt(0) would drain the DMA ring.  The s_barrier
+// intrinsic does not order memory operations for the compiler: fenced on both sides (as
+// k_match_raw, sift_match.hip)
+__device__ __forceinline__ void coop_barrier() {
+    asm volatile("" ::: "memory");
+    wait_lgkm0();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 
 // 32: strips of 96 columns for both compiled pairs; 128 x 1080p, (11, 13): 784 us against 905 for
 // the unaligned 116-column strips (tests/diag/r05e.sh; 16, 64-B lines: 820)
@@ -145,8 +170,10 @@ __device__ __forceinline__ void duo_zero(const ZeroJob& z) {
 
 // DS: 0 no decimation, 1 level k + 1 (stage A) into the next octave's level 0, 2 level k + 2
 // (stage B)
-template <int FWA, int FWB, int NIN, bool U8, int DS>
-__device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, float* s_mid) {
+// COOP: the cooperative form (the file header): gw counts workgroups' waves (4 per strip and band),
+// wv is the wave's place in its workgroup, s_mid the workgroup's shared mid rows
+template <int FWA, int FWB, int NIN, bool U8, int DS, bool COOP>
+__device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, int wv, float* s_in, float* s_mid) {
     using G = DuoGeom<FWA, FWB>;
     constexpr int RA = G::RA, RB = G::RB, SW = G::SW, NDMA = G::NDMA, IN_SLOT = G::IN_SLOT;
     constexpr int P = G::P, U = G::U, MOFF = G::MOFF, OB = G::OB, NQ = G::NQ;
@@ -156,7 +183,7 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
     constexpr bool kX4 = SGK_DUO_EXP == 3 || SGK_DUO_EXP == 4;
     // the shipped 16-B DMA, for the pairs of < 40 taps: (21, 25)'s register budget (168 VGPRs at
     // 3 waves per SIMD) does not take the second walk copy (a VGPR spill, 1,265 vs 987 us)
-    constexpr bool kRowX4 = SGK_DUO_X4 && !U8 && SGK_DUO_EXP == 0 && FWA + FWB < 40;
+    constexpr bool kRowX4 = SGK_DUO_X4 && !U8 && (SGK_DUO_EXP == 0 || SGK_DUO_EXP == 5) && FWA + FWB < 40;
     constexpr int D = G::D, NQ4 = G::NQ4;
     static_assert(!kRowX4 || (8 * NQ4 <= IN_SLOT && 2 * NQ4 > 64 && 2 * NQ4 <= 128), "X4 slot");
     // (X4: the interior strips' 2 DMAs; the edge strips keep 5 per-column DMAs, OPSE)
@@ -165,10 +192,27 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
     static_assert(NIN >= 2 && OPSE * (NIN - 1) < 64, "DMA ring (vmcnt field)");
     const int lane = threadIdx.x & 63;
     const int W = J.W, H = J.H;
-    const int sx = gw % J.strips, rest = gw / J.strips;
+    const int unit = COOP ? gw / kDuoWaves : gw;   // (strip, band, image): a workgroup's or a wave's
+    const int sx = unit % J.strips, rest = unit / J.strips;
     const int sy = rest % J.nsy, b = rest / J.nsy;
-    const int x0 = sx * SW;
+    // cooperative: the wave's part of the workgroup's strip (sift_gauss_coop_plan.h)
+    const coop::Wave cw = coop::wave_plan(W, FWB, sx, wv);
+    static_assert(!COOP || coop::moff(FWB) == MOFF, "cooperative geometry");
+    const int xs = COOP ? cw.xs : sx * SW;         // first output column of the strip
+    const int x0 = COOP ? cw.x0 : xs;              // first output column of the wave (stage B)
     const int yb = sy * J.rows_per_band, ye = min(H, yb + J.rows_per_band);
+    const int ntau = (ye - yb) + 2 * RA + 2 * RB + 2;
+    const int nsteps = (ntau + 1) / 2;
+    const int niter = (nsteps + U - 1) / U;
+    if constexpr (COOP) {
+        // a wave whose mid columns all lie outside the image computes nothing, writes nothing and
+        // keeps the workgroup's barriers, one per step (yb, ye and so the step count are the
+        // workgroup's)
+        if (cw.outside) {
+            for (int t = 0; t < niter * U; t++) coop_barrier();
+            return;
+        }
+    }
     const int m0 = x0 - MOFF;      // mid column of lane 0's first column (even)
     const int a0 = m0 - RA;        // input column of the input slot's float2 0
     const float* src = U8 ? nullptr : J.src + (long long)b * J.src_img;
@@ -263,13 +307,19 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
 
     // ---- lane roles
     const int c = m0 + 2 * lane;                       // mid columns c, c + 1 (stage A)
-    const bool own1 = c >= x0 && c < x0 + SW && c < W; // stage A stores these columns
-    const int le = lane < SW / 2 ? lane : SW / 2 - 1;  // stage B lane (idle lanes repeat the last)
+    // stage A stores these columns (cooperative: the strip's, waves 0 and 3 hold its halo columns)
+    const bool own1 = COOP ? c >= cw.own_lo && c < cw.own_hi : c >= x0 && c < x0 + SW && c < W;
+    const int NB = COOP ? cw.nb : SW / 2;              // stage B lanes (cooperative: 64, wave 3 48)
+    const int le = lane < NB ? lane : NB - 1;          // stage B lane (idle lanes repeat the last)
     const int e = x0 + 2 * le;                         // output columns e, e + 1 (stage B)
-    const bool own2 = lane < SW / 2 && e < W;
-    const bool left = m0 < 0, right = m0 + 128 > W;    // uniform: edge strips
+    const bool own2 = lane < NB && e < W;
+    // uniform: edge strips (cooperative: the waves that hold column 0 / column W-1)
+    const bool left = m0 < 0, right = COOP ? cw.right : m0 + 128 > W;
     const int l_left = left ? (-m0) >> 1 : 0;          // lane holding mid column 0 (as .x)
     const int l_right = right ? (W - 2 - m0) >> 1 : 0; // lane holding mid column W-1 (as .y)
+    // cooperative: a wave of the last strip may hold mid columns and no output column; the skipped
+    // stage B stores would leave the counted wait short of the step's DMA: such a wave drains
+    const bool drain = COOP && !U8 && x0 >= W;
     // mid row pair of one lane (columns c, c+1) clamped to the image's edge columns
     // (in the edge strips only: the lanes' columns outside the image; l_left / l_right are 0
     // when there is no such edge, and no lane then has c < 0 / c >= W)
@@ -374,10 +424,25 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
     };
     // mid slots: 0, 1 alternate (stage A writes step t's pair into slot t & 1, stage B reads the
     // previous step's from the other), 2 = (mid 0, mid 0), 3 = (mid H-1, mid H-1)
-    float* const mid_top = s_mid + 2 * kMidSlot;
-    float* const mid_bot = s_mid + 3 * kMidSlot;
+    // cooperative: a slot is the workgroup's row of 512 columns, the waves' blocks side by side;
+    // a wave writes its own block and stage B's operands run into the neighbours' (one workgroup
+    // barrier per step between the two)
+    constexpr int MS = COOP ? kDuoWaves * kMidSlot : kMidSlot;   // floats of one slot
+    float* const s_midw = s_mid + (COOP ? wv * kMidSlot : 0);    // the wave's block of slot 0
+    float* const mid_top = s_midw + 2 * MS;
+    float* const mid_bot = s_midw + 3 * MS;
     auto put_mid = [&](float* slot, f2v r0, f2v r1) __attribute__((always_inline)) {
         reinterpret_cast<float4*>(slot)[lane] = make_float4(r0.x, r1.x, r0.y, r1.y);
+        if constexpr (COOP) {
+            // the clamped columns past the wave's block (the wave that holds column W-1): its
+            // value into the first cw.spill float4s of the next wave's block, which that wave
+            // (outside the image) never writes
+            if (cw.spill > 0) {
+                const float e0 = readlane_f(r0.y, l_right), e1 = readlane_f(r1.y, l_right);
+                if (lane < cw.spill)
+                    reinterpret_cast<float4*>(slot)[64 + lane] = make_float4(e0, e1, e0, e1);
+            }
+        }
     };
 
     // ---- top band: mid row 0 (the rows above 0 clamp to it) before the walk, as the pull sum
@@ -430,10 +495,11 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
     // ---- the walk.  Step t: stage A pushes input rows rho0 + 2t, + 1 and completes the mid pair
     // mc = rho0 + 2t - RA, + 1; stage B pushes the pair stage A completed in step t - 1 (mc - 2),
     // so the two H passes of a step are independent and their fma chains interleave.
+    // Cooperative: one workgroup barrier at the head of each step, between every wave's put_mid
+    // of step t - 1 (and the top band's mid_top) and the h2 of step t.  Slot t & 1 is written in
+    // step t, read in step t + 1 and written again in step t + 2, after the barrier that every
+    // wave reaches with step t + 1's reads complete.
     const int rho0 = yb - RB - RA;
-    const int ntau = (ye - yb) + 2 * RA + 2 * RB + 2;
-    const int nsteps = (ntau + 1) / 2;
-    const int niter = (nsteps + U - 1) / U;
     f2v accA[P], accB[P];
 #pragma unroll
     for (int i = 0; i < P; i++) {
@@ -509,14 +575,17 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
                     // the previous NIN - 2 steps' DMAs and stores, and the stores of the step that
                     // issued step t's DMA -- has completed: step t's DMA has landed
                     wait_vm<OPSW * (NIN - 1)>();
+                    if constexpr (COOP) {
+                        if (drain) wait_vm<0>();
+                    }
                 }
+                if constexpr (COOP || SGK_DUO_EXP == 5) coop_barrier();
                 asm volatile("" ::: "memory");
                 // both H passes: stage A on the input slot, stage B on the previous step's mid pair
                 // (an offset from one base: a select between the slot pointers made the compiler
                 // lose their LDS address space -- flat accesses through the lambdas' closure)
-                const int mb_off = mu <= -1 ? 2 * kMidSlot : (mu >= H - 1 ? 3 * kMidSlot
-                                                                          : (mid_cur ^ 1) * kMidSlot);
-                const float* mb = s_mid + mb_off;
+                const int mb_off = mu <= -1 ? 2 * MS : (mu >= H - 1 ? 3 * MS : (mid_cur ^ 1) * MS);
+                const float* mb = s_midw + mb_off;
                 f2v q0, q1, r0, r1;
                 if constexpr (kRowX4) {
                     h1rows(slot_use * IN_SLOT, r0, r1);
@@ -562,7 +631,7 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
                     fix_edges(A0);
                     fix_edges(A1);
                 }
-                put_mid(s_mid + mid_cur * kMidSlot, A0, A1);
+                put_mid(s_midw + mid_cur * MS, A0, A1);
                 mid_cur ^= 1;
                 if (mc <= H - 1 && mc + 1 >= H - 1) {
                     const f2v Bv = mc == H - 1 ? A0 : A1;
@@ -616,7 +685,9 @@ __device__ __forceinline__ void duo_wave(const DuoJob& J, int gw, float* s_in, f
 #ifndef SGK_DUO_WPE_NARROW
 #define SGK_DUO_WPE_NARROW 4
 #endif
-template <int FWA, int FWB, int NIN, bool U8, int DS>
+// COOP: the same LDS (the four waves' mid slots are the workgroup's four shared rows), registers
+// and so occupancy as the per-wave form
+template <int FWA, int FWB, int NIN, bool U8, int DS, bool COOP>
 __global__ __launch_bounds__(64 * kDuoWaves) __attribute__((amdgpu_waves_per_eu(FWA + FWB >= 30 ? SGK_DUO_WPE_WIDE : SGK_DUO_WPE_NARROW))) void k_gauss_duo(const DuoJob J) {
     using G = DuoGeom<FWA, FWB>;
     // u8 input: one input slot (the registers hold the prefetched rows)
@@ -625,8 +696,10 @@ __global__ __launch_bounds__(64 * kDuoWaves) __attribute__((amdgpu_waves_per_eu(
     if (J.zero.n[0] | J.zero.n[1] | J.zero.n[2]) duo_zero(J.zero);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int gw = ring_block(blockIdx.x, gridDim.x) * kDuoWaves + wave;
-    if (gw >= J.total_waves) return;   // uniform per wave
-    duo_wave<FWA, FWB, NIN, U8, DS>(J, gw, s_in_all[wave], s_mid_all[wave]);
+    // uniform per wave; cooperative: per workgroup (total_waves is a multiple of 4 -- a wave that
+    // left would be missed at the barriers)
+    if (gw >= J.total_waves) return;
+    duo_wave<FWA, FWB, NIN, U8, DS, COOP>(J, gw, wave, s_in_all[wave], COOP ? s_mid_all[0] : s_mid_all[wave]);
 }
 
 // input row pairs in LDS: the DMA runs NIN - 1 steps ahead (compiled: 4, 5 and 7; SGPU_DUO_NIN
@@ -663,9 +736,26 @@ static long long duo_waves_target() {
     return v;
 }
 
-template <int FWA, int FWB, bool U8, int DS>
-hipError_t duo_launch(const LevelOp& a, const LevelOp& b, hipStream_t stream, int rows_hint,
-                      float* trash) {
+// the cooperative form is compiled for the pairs that run on 1920 and 960 columns: all but the
+// front plan's (17, 21)
+template <int FWA, int FWB>
+constexpr bool kDuoCoopCompiled = !(FWA == 17 && FWB == 21);
+// ... and taken by the rule (fewer issued lane-columns, coop::fewer_lane_columns) for the pairs
+// where it measured faster (all four, 4 - 12 % per launch at 1920 / 960 columns),
+// on levels of at most SGK_DUO_COOP_MAXW columns: C4's 4096- and 2048-column levels measured no
+// gain (pyramid 3.62 - 3.64 against 3.62 - 3.65 ms) and keep the per-wave strips
+#ifndef SGK_DUO_COOP_RULE
+#define SGK_DUO_COOP_RULE 1
+#endif
+#ifndef SGK_DUO_COOP_MAXW
+#define SGK_DUO_COOP_MAXW 1920
+#endif
+template <int FWA, int FWB>
+constexpr bool kDuoCoopRule = SGK_DUO_COOP_RULE != 0 && SGK_DUO_EXP == 0 && kDuoCoopCompiled<FWA, FWB>;
+
+template <int FWA, int FWB, bool U8, int DS, bool COOP>
+hipError_t duo_launch_form(const LevelOp& a, const LevelOp& b, hipStream_t stream, int rows_hint,
+                           float* trash) {
     using G = DuoGeom<FWA, FWB>;
     DuoJob J{};
     J.src = a.src;
@@ -685,8 +775,9 @@ hipError_t duo_launch(const LevelOp& a, const LevelOp& b, hipStream_t stream, in
     J.dsw = dl.ds_w;
     J.dsh = dl.ds_h;
     J.ds_img = dl.ds_img_stride;
-    J.strips = (a.w + G::SW - 1) / G::SW;
-    const long long per_band = (long long)J.strips * a.batch;
+    // cooperative: a strip is a workgroup's (4 waves), so total_waves is a multiple of 4
+    J.strips = COOP ? coop::strips(a.w, FWB) : (a.w + G::SW - 1) / G::SW;
+    const long long per_band = (long long)J.strips * a.batch * (COOP ? kDuoWaves : 1);
     // bands: as many as the grid needs for duo_waves_target() waves; each band re-walks
     // 2 (RA + RB) halo rows, so bands stay >= 64 rows
     int nsy = 1;
@@ -706,14 +797,29 @@ hipError_t duo_launch(const LevelOp& a, const LevelOp& b, hipStream_t stream, in
     J.trash = trash;
     const unsigned nb = (unsigned)((J.total_waves + kDuoWaves - 1) / kDuoWaves);
     if constexpr (U8)
-        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 2, true, DS>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
+        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 2, true, DS, COOP>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
+    else if constexpr (COOP)   // (the cooperative form with the shipped ring only)
+        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 7, false, DS, true>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
     else if (duo_nin() == 5)
-        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 5, false, DS>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
+        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 5, false, DS, false>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
     else if (duo_nin() == 4)   // 36,864 B of LDS per workgroup: 4 workgroups (16 waves) per CU
-        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 4, false, DS>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
+        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 4, false, DS, false>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
     else
-        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 7, false, DS>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
+        hipLaunchKernelGGL((k_gauss_duo<FWA, FWB, 7, false, DS, false>), dim3(nb), dim3(64 * kDuoWaves), 0, stream, J);
     return hipGetLastError();
+}
+
+// strips: kDuoStrips* (sift_kernels.h; sgpu_debug_set_duo_strips)
+template <int FWA, int FWB, bool U8, int DS>
+hipError_t duo_launch(const LevelOp& a, const LevelOp& b, hipStream_t stream, int rows_hint,
+                      float* trash, int strips) {
+    if constexpr (kDuoCoopCompiled<FWA, FWB>) {
+        const bool rule = kDuoCoopRule<FWA, FWB> && a.w <= SGK_DUO_COOP_MAXW &&
+                          coop::fewer_lane_columns(a.w, FWB);
+        if (strips == kDuoStripsCoop || (strips == kDuoStripsRule && rule))
+            return duo_launch_form<FWA, FWB, U8, DS, true>(a, b, stream, rows_hint, trash);
+    }
+    return duo_launch_form<FWA, FWB, U8, DS, false>(a, b, stream, rows_hint, trash);
 }
 
 }  // namespace
@@ -745,13 +851,13 @@ bool gauss_duo_supported(const LevelOp& a, const LevelOp& b) {
 }
 
 hipError_t launch_gauss_duo(const LevelOp& a, const LevelOp& b, hipStream_t stream, int rows_hint,
-                            float* trash) {
+                            float* trash, int strips) {
     if (!trash || !gauss_duo_supported(a, b)) return hipErrorInvalidValue;
-    if (a.src_u8) return duo_launch<13, 11, true, 0>(a, b, stream, rows_hint, trash);
-    if (a.ds_dst) return duo_launch<17, 21, false, 1>(a, b, stream, rows_hint, trash);
-    if (b.ds_dst) return duo_launch<13, 17, false, 2>(a, b, stream, rows_hint, trash);
+    if (a.src_u8) return duo_launch<13, 11, true, 0>(a, b, stream, rows_hint, trash, strips);
+    if (a.ds_dst) return duo_launch<17, 21, false, 1>(a, b, stream, rows_hint, trash, strips);
+    if (b.ds_dst) return duo_launch<13, 17, false, 2>(a, b, stream, rows_hint, trash, strips);
 #define SGK_DUO(A, B) \
-    if (a.fw == A && b.fw == B) return duo_launch<A, B, false, 0>(a, b, stream, rows_hint, trash);
+    if (a.fw == A && b.fw == B) return duo_launch<A, B, false, 0>(a, b, stream, rows_hint, trash, strips);
     SGK_DUO(11, 13) SGK_DUO(21, 25)
 #undef SGK_DUO
     return hipErrorInvalidValue;

@@ -94,11 +94,15 @@ hipError_t launch_gauss_two(const LevelOp& a, const LevelOp& b, hipStream_t stre
 // the next octave's level 0, (13, 17) with level k+2 decimated); or the u8 ingest pair (13, 11),
 // level 0 from the image and level 1 (with a's ZeroJob): 9 B instead of 13.  Bit-identical to two
 // launch_gauss_op calls.  trash: kGaussDuoTrashBytes of device scratch.  rows_hint > 0 forces
-// the band height.
+// the band height.  strips: the strip geometry (SGPU_DUO_STRIPS_* of sgpu.h) -- the rule
+// (cooperative strips of 480 columns per workgroup, sift_gauss_coop_plan.h, where they issue fewer
+// lane-columns than the per-wave strips of 96 and the pair measured faster), per-wave always, or
+// cooperative wherever it is compiled; the same bits in every form.
 constexpr size_t kGaussDuoTrashBytes = 1024 * 3072;
+constexpr int kDuoStripsRule = 0, kDuoStripsWave = 1, kDuoStripsCoop = 2;
 bool gauss_duo_supported(const LevelOp& a, const LevelOp& b);
 hipError_t launch_gauss_duo(const LevelOp& a, const LevelOp& b, hipStream_t stream, int rows_hint,
-                            float* trash);
+                            float* trash, int strips = kDuoStripsRule);
 
 // Three consecutive levels in one launch (sift_gauss_trio.hip): a = level k -> k+1, b = k+1 ->
 // k+2, c = k+2 -> k+3 (b.src == a.dst, c.src == b.dst) with level k+3 decimated into the next

@@ -36,6 +36,7 @@ C_API = [
     "sgpu_set_host_output", "sgpu_debug_set_schedule", "sgpu_debug_set_match_prune",
     "sgpu_quantize_descriptors_gpu", "sgpu_feature_descriptors_u8", "sgpu_copy_features_u8",
     "sgpu_match_batch", "sgpu_match_images", "sgpu_debug_match_plan_stats",
+    "sgpu_debug_set_duo_strips",
 ]
 
 _LIB = None
@@ -85,6 +86,7 @@ def lib():
         L.sgpu_debug_set_flags.argtypes = [vp, c.c_int]
         L.sgpu_debug_set_schedule.argtypes = [vp, c.c_int, c.c_int]
         L.sgpu_debug_set_match_prune.argtypes = [vp, c.c_int]
+        L.sgpu_debug_set_duo_strips.argtypes = [vp, c.c_int]
         L.sgpu_debug_geometry.argtypes = [vp, P(c.c_int), vp, c.c_int]
         L.sgpu_debug_gaussian.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
         L.sgpu_debug_candidates.argtypes = [vp, vp, vp, c.c_int, P(c.c_int)]
@@ -597,6 +599,15 @@ class SiftContext:
         decimation allow) and the octave's level pairs from its end (PAIRS_END, shipped) or its
         front (PAIRS_FRONT)."""
         self._check(lib().sgpu_debug_set_schedule(self._ctx, trio, pairs), "sgpu_debug_set_schedule")
+
+    STRIPS_RULE, STRIPS_WAVE, STRIPS_COOP = 0, 1, 2
+
+    def set_duo_strips(self, mode: int = 0):
+        """Strip geometry of the paired-level launches (sgpu_debug_set_duo_strips): STRIPS_RULE
+        (shipped: a workgroup's four waves share a 480-column strip where that issues fewer
+        lane-columns and measured faster), STRIPS_WAVE (a 96-column strip per wave everywhere),
+        STRIPS_COOP (the shared strip wherever it is compiled, at any width): the same levels."""
+        self._check(lib().sgpu_debug_set_duo_strips(self._ctx, mode), "sgpu_debug_set_duo_strips")
 
     def set_match_prune(self, on: bool = True):
         """Plain mutual matching's column side over the rows of set 1 that can change a listed
