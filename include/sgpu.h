@@ -400,6 +400,24 @@ int sgpu_debug_set_match_prune(sgpu_ctx* ctx, int on);
  * with no pair of two non-empty sets).  SGPU_EINVAL before the first such call and after one whose
  * offsets or pair indices were rejected.  Tests use it to prove which plan regime they ran in. */
 int sgpu_debug_match_plan_stats(const sgpu_ctx* ctx, long long out[4]);
+/* The launch list of the last extract's Gaussian pyramid (part 0) as its planner made it
+ * (csrc/sift_pyramid_plan.h), read-only, in issue order.  Returns the number of
+ * entries and writes the first cap / SGPU_PLAN_ENTRY_INTS of them to out (cap ints; 0 with out
+ * NULL just counts): per entry {kind, o0, k0, o1, k1, o2, k2} -- kind one of SGPU_PLAN_*, then the
+ * (octave, level written) of each level filter of the launch, (-1, -1) where the kind has fewer.
+ * An entry of a "two" kind can take one or two kernel launches (sgpu_last_pyramid_launches counts
+ * those).  SGPU_EINVAL before the first extract.  Tests use it to prove which launches ran. */
+#define SGPU_PLAN_ENTRY_INTS 7
+#define SGPU_PLAN_LEVEL 0        /* one level, wave kernels (k_gauss_lean / k_gauss_pk2)        */
+#define SGPU_PLAN_TILE 1         /* one level in 2-D tiles (k_gauss_tile)                       */
+#define SGPU_PLAN_TWO 2          /* two independent levels, wave kernels                        */
+#define SGPU_PLAN_TILE_TWO 3     /* two independent tiled levels                                */
+#define SGPU_PLAN_TILE_DUO 4     /* two consecutive levels per tile (k_gauss_tile_duo)          */
+#define SGPU_PLAN_TILE_DUO_ONE 5 /* a tile duo beside an independent tiled level                */
+#define SGPU_PLAN_DUO 6          /* paired levels (k_gauss_duo)                                 */
+#define SGPU_PLAN_TRIO 7         /* three levels (k_gauss_trio)                                 */
+#define SGPU_PLAN_KINDS 8
+int sgpu_debug_pyramid_plan(const sgpu_ctx* ctx, int* out, int cap);
 /* Octave geometry of the last extract: n_octaves, and (w, h, wa) per octave. */
 int sgpu_debug_geometry(const sgpu_ctx* ctx, int* n_octaves, int* dims /* 3*max */, int max);
 /* Gaussian level (image, octave, level 0..level_num-1) as wa*h floats. */

@@ -27,49 +27,9 @@
 #include "sift_kernels.h"
 #include "sift_match_plan.h"
 #include "sift_params.h"
+#include "sift_pyramid_plan.h"
 
 namespace {
-
-// paired-level Gaussian launches in the shipped schedule (1), or only when asked for by
-// SGPU_DUO=on / the debug flags (0)
-#ifndef SGK_DUO_DEFAULT
-#define SGK_DUO_DEFAULT 1
-#endif
-// paired-level Gaussian launches only for levels of at least this many MB (smaller ones stay in
-// the Infinity Cache between launches and are latency-bound: one level per launch, 1-chunk bands)
-#ifndef SGK_DUO_MIN_MB
-#define SGK_DUO_MIN_MB 128
-#endif
-// paired levels: (11, 13) from SGK_DUO_MIN_MB; (17, 21) with the decimation, whose arithmetic
-// makes it latency-bound on smaller levels, from SGK_DUO_WIDE_MIN_MB (128 x 1080p: octave 0
-// 903 us against 1,052 for two launches; octave 1 309 against ~270, tests/diag/r05i.sh); (21, 25)
-// only by SGPU_DUO_WIDE=1 (1,016 us against ~1,050, and it would take level 4 from (17, 21))
-#ifndef SGK_DUO_WIDE_MIN_MB
-#define SGK_DUO_WIDE_MIN_MB 512
-#endif
-// three levels per launch (k_gauss_trio: widths (11, 13, 17), the third decimated into the next
-// octave) for levels of at least this many MB; the octave's remaining (21, 25) pair then runs as a
-// paired-level launch
-// the octave's level pairs taken from its end ((4, 5), (2, 3) with the decimation, (0, 1)): 1,
-// or from its front: 0 (sgpu_ctx::duo_plan); from the end only on levels of at most
-// SGK_DUO_PLAN_MAXW columns (128 x 1080p: octave 0 2.575 vs 2.613 ms; 16 x 4096^2 (C4): 2.87 vs
-// 2.80 ms -- every paired-level launch of the 4096-column levels runs ~10 % slower than on 1920
-// columns)
-#ifndef SGK_DUO_PLAN
-#define SGK_DUO_PLAN 1
-#endif
-#ifndef SGK_DUO_PLAN_MAXW
-#define SGK_DUO_PLAN_MAXW 2048
-#endif
-#ifndef SGK_TRIO_MIN_MB
-#define SGK_TRIO_MIN_MB 512
-#endif
-
-// 2-D tile launches (k_gauss_tile, sift_gauss_tile.hip) for levels of at most this many MB (one
-// 1080p image: 8.3 MB at octave 0), where the wave walk of k_gauss_lean is latency-bound
-#ifndef SGK_TILE_MB
-#define SGK_TILE_MB 16
-#endif
 
 // feature counts (of the previous call) up to which each descriptor gets a workgroup of 4 waves
 // (k_descriptor_wide): ~1,500 features of one 1080p image are ~1.5 waves per SIMD under one wave
@@ -122,6 +82,11 @@ struct Part {
     hipEvent_t ev_oct = nullptr;       // octaves >= 1 done
     size_t cand_hint = 0, feat_hint = 0;   // counts of the previous call (launch-grid sizing)
     int gauss_launches = 0, gauss_filters = 0;   // the last pyramid: launches, level filters
+    // the last pyramid's level filters (build_level_ops), what the planner reads of them, and its
+    // launch list (sift_pyramid_plan.h; sgpu_debug_pyramid_plan); kept across calls for their storage
+    std::vector<sgk::LevelOp> ops;
+    std::vector<sgpyr::LevelDesc> levels;
+    sgpyr::Plan plan;
     bool events = true;                    // the last enqueue recorded its stage events
     bool copied_out = false;               // the last enqueue copied its results to host_out
     hipEvent_t ev[10] = {};  // start, pyramid, detect, orientation, expand, descriptor, end,
@@ -655,37 +620,18 @@ static int layout_part(sgpu_ctx* ctx, Part& pt) {
     return SGPU_OK;
 }
 
-// Queue the whole pipeline of one part on its stream.  `wait` (may be null) is an event the
-// part's pyramid must wait for.  No host synchronisation.
-static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32, int stride,
-                        hipEvent_t wait, hipEvent_t wait_lo = nullptr) {
-    hipStream_t st = pt.stream;   // reassigned per stage below
+// The level filters of every octave of a part's pyramid into pt.ops, and what the planner reads
+// of them into pt.levels: op (o, k) filters level k-1 into level k (op (0, 0) smooths the input
+// into level 0); level kds = level_ds - level_min of octave o also writes its 2x decimation as
+// level 0 of octave o+1 (PyramidCU.cpp:1024).  With -fo != 0 it first queues the input's
+// resampling on st.
+static int build_level_ops(sgpu_ctx* ctx, Part& pt, const uint8_t* src8, const float* srcf,
+                           int stride, hipStream_t st) {
     const sgpu_options& O = ctx->opt;
     const sgp::Schedule& S = ctx->sched;
-    const int nlev = S.level_num;
-    const int noct = (int)ctx->oct.size();
-    const int n = pt.n, h = ctx->h;
-    const int rc_layout = layout_part(ctx, pt);
-    if (rc_layout != SGPU_OK) return rc_layout;
     const sgk::FeatureParams& fp = pt.fp;
-    const long long moff = pt.mask_words;
-    const size_t nc = pt.cand_cap, ne_cap = 2 * nc;
-
-    if (wait) HIPCHK(ctx, hipStreamWaitEvent(st, wait, 0));
-    // stage events: always where a stream waits on them (the multi-stream layouts, the
-    // host-in / host-out stream), else only when the context times its stages
-    pt.events = ctx->stage_timing || !pt.one_stream || ctx->nparts > 1 || ctx->streaming;
-    auto rec = [&](int i, hipStream_t s_) -> hipError_t {
-        return pt.events ? hipEventRecord(pt.ev[i], s_) : hipSuccess;
-    };
-    HIPCHK(ctx, rec(0, st));
+    const int nlev = S.level_num, noct = (int)ctx->oct.size(), n = pt.n, h = ctx->h;
     const size_t img_elems = (size_t)stride * h;
-    const uint8_t* src8 = is_f32 ? nullptr : (const uint8_t*)src_in + (size_t)pt.img0 * img_elems;
-    const float* srcf = is_f32 ? (const float*)src_in + (size_t)pt.img0 * img_elems : nullptr;
-
-    // ---- Gaussian pyramid (BuildPyramid, PyramidCU.cpp:979-1044): one launch per level
-    // (k_gauss_wave) for the whole part.  Level kds = level_ds - level_min of octave o also writes
-    // its 2x decimation as level 0 of octave o+1 (PyramidCU.cpp:1024).
     float* pyr = pt.pyr.as<float>();
     sgk::Taps ltaps[sgk::kMaxLevels], taps0;
     int lfw[sgk::kMaxLevels] = {0};
@@ -693,35 +639,10 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
         lfw[k] = sgp::make_filter(S.sigma[k - 1], O.filter_width_factor, ltaps[k].k);
     const int fw0 = sgp::make_filter(S.initial_smooth, O.filter_width_factor, taps0.k);
     const int kds = S.level_ds - S.level_min;
-    // Stream layout (SGPU_STREAMS=multi, not the default: extract_body): octaves >= 1 run on a
-    // second stream, which starts as soon as octave 0's level kds has written octave 1's base
-    // (level 0), so their small launches run beside octave 0's last levels (pyramid 3.64 vs
-    // 3.69-3.74 ms per 128 x 1080p), and the main stream waits for them before
-    // the extremum kernel.  SGPU_DEBUG_PYR_SERIAL: one stream for the pyramid only.
-    const bool side = noct > 1 && !pt.one_stream && !(ctx->debug_flags & SGPU_DEBUG_PYR_SERIAL);
-    const int wave_rows = (ctx->debug_flags & SGPU_DEBUG_GAUSS_BLOCK)
-                              ? -1 : ((ctx->debug_flags >> SGPU_DEBUG_BAND_SHIFT) & 0x7ff);
-    const bool long_bands = (ctx->debug_flags & SGPU_DEBUG_GAUSS_LONG_BANDS) != 0;
-    // 2-D tiles for the cache-resident levels (sift_gauss_tile.hip): not with a forced kernel or
-    // band height (those test the wave kernels)
-    const bool tiles_on = wave_rows == 0 && !long_bands &&
-                          !(ctx->debug_flags & SGPU_DEBUG_GAUSS_TILE_OFF);
-    const bool tiles_all = tiles_on && (ctx->debug_flags & SGPU_DEBUG_GAUSS_TILE_ALWAYS);
-    auto tiled = [&](const sgk::LevelOp& op) {
-        return tiles_on && sgk::gauss_tile_supported(op) &&
-               (tiles_all || 4ll * op.w * op.h * op.batch <= ((long long)ctx->tile_mb << 20));
-    };
-    auto level = [&](const sgk::LevelOp& op, hipStream_t s_) {
-        return tiled(op) ? sgk::launch_gauss_tile(op, s_)
-                         : sgk::launch_gauss_op(op, s_, wave_rows, long_bands);
-    };
-    // the level filters of every octave: op (o, k) filters level k-1 into level k (op (0, 0)
-    // smooths the input into level 0); level kds of octave o also writes its decimation, level 0
-    // of octave o+1
-    struct Op { sgk::LevelOp op; int o, k; };
-    std::vector<Op> ops;
-    pt.gauss_launches = 0;   // kernel launches of the level filters (sgpu_last_pyramid_launches)
-    ops.reserve((size_t)noct * nlev);
+    pt.ops.clear();
+    pt.levels.clear();
+    pt.ops.reserve((size_t)noct * nlev);
+    pt.levels.reserve((size_t)noct * nlev);
     for (int o = 0; o < noct; o++) {
         const sgk::OctaveDesc& od = fp.oct[o];
         const long long npx = (long long)od.wa * od.h;
@@ -753,10 +674,8 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
             in_img = npx;
         }
         for (int k = (o == 0 ? 0 : 1); k < nlev; k++) {
-            Op e{};
-            e.o = o;
-            e.k = k;
-            sgk::LevelOp& op = e.op;
+            pt.ops.emplace_back();
+            sgk::LevelOp& op = pt.ops.back();
             op.fw = k == 0 ? fw0 : lfw[k];
             const float* tk = k == 0 ? taps0.k : ltaps[k].k;
             for (int i = 0; i < op.fw; i++) op.taps.k[i] = tk[i];
@@ -780,226 +699,125 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
                 op.zero.p[0] = pt.row_count.as<uint32_t>();
                 op.zero.n[0] = (size_t)pt.total_rows;
                 op.zero.p[1] = pt.mask.as<uint32_t>();
-                op.zero.n[1] = (size_t)moff;
+                op.zero.n[1] = (size_t)pt.mask_words;
                 op.zero.p[2] = pt.ocount.as<uint32_t>();
-                op.zero.n[2] = nc;
+                op.zero.n[2] = pt.cand_cap;
             }
-            ops.push_back(e);
+            pt.levels.push_back(sgpyr::LevelDesc{o, k, op.fw, op.w, op.h, op.batch, dk,
+                                                 op.src_u8 != nullptr,
+                                                 (op.zero.n[0] | op.zero.n[1] | op.zero.n[2]) != 0});
         }
     }
-    pt.gauss_filters = (int)ops.size();
-    // every level tiled (a cache-resident pyramid: one image, C2) and tile duos asked for
-    // (SGPU_TILE_DUO=on, or SGPU_DEBUG_DUO_ALWAYS with SGPU_DEBUG_GAUSS_TILE_ALWAYS): the tile-duo
-    // schedule -- octave
-    // 0 pairs levels (0, 1), (2, 3), (4, 5) into tile duos (two levels per launch from one load,
-    // sift_gauss_tile.hip), octaves >= 1 run level 1 alone and pair the rest; a job launches right
-    // after the job holding its input, and octave o+1's level 1 shares the launch of octave o's last
-    // duo (-no 4 -d 3: 9 launches instead of 15).  Measured slower than the single-level tiles of
-    // the diagonal schedule (C2 pyramid 115-119 vs 97-99 us: a duo tile's stage-1 halo region and
-    // its five barrier phases cost more than the launch and the level's round trip it saves,
-    // DESIGN.md 4.6), so not the default.
-    const bool want_duo = ctx->tile_duo || ((ctx->debug_flags & SGPU_DEBUG_DUO_ALWAYS) &&
-                                            (ctx->debug_flags & SGPU_DEBUG_GAUSS_TILE_ALWAYS));
-    bool all_tiled = want_duo && !side && !(ctx->debug_flags & SGPU_DEBUG_PYR_SERIAL) &&
-                     kds >= 1 && !ops.empty();
-    for (const Op& e : ops) all_tiled = all_tiled && tiled(e.op);
-    if (all_tiled) {
-        struct Job { size_t i0; int n, launch; };
-        std::vector<Job> jobs;
-        std::vector<int> job_of(ops.size(), -1);
-        auto op_index = [&](int o, int k) -> int {
-            for (size_t i = 0; i < ops.size(); i++)
-                if (ops[i].o == o && ops[i].k == k) return (int)i;
-            return -1;
-        };
-        for (size_t i = 0; i < ops.size();) {
-            const Op& e = ops[i];
-            const bool pair = e.k % 2 == 0 && i + 1 < ops.size() && ops[i + 1].o == e.o &&
-                              ops[i + 1].k == e.k + 1 &&
-                              sgk::gauss_tile_duo_supported(e.op, ops[i + 1].op);
-            jobs.push_back({i, pair ? 2 : 1, 0});
-            job_of[i] = (int)jobs.size() - 1;
-            if (pair) job_of[i + 1] = (int)jobs.size() - 1;
-            i += pair ? 2 : 1;
+    pt.gauss_filters = (int)pt.ops.size();
+    return SGPU_OK;
+}
+
+// The planner's support queries, answered from the real level filters.
+struct OpSupport {
+    const sgk::LevelOp* op;
+    bool tile(int i) const { return sgk::gauss_tile_supported(op[i]); }
+    bool tile_duo(int i, int j) const { return sgk::gauss_tile_duo_supported(op[i], op[j]); }
+    bool duo(int i, int j) const { return sgk::gauss_duo_supported(op[i], op[j]); }
+    bool trio(int i, int j, int l) const { return sgk::gauss_trio_supported(op[i], op[j], op[l]); }
+};
+
+// The planner's rules from the context's switches and debug flags.
+// Stream layout (SGPU_STREAMS=multi, not the default: extract_body): octaves >= 1 run on a second
+// stream, which starts as soon as octave 0's level kds has written octave 1's base (level 0), so
+// their small launches run beside octave 0's last levels (pyramid 3.64 vs 3.69-3.74 ms per 128 x
+// 1080p), and the main stream waits for them before the extremum kernel.
+// SGPU_DEBUG_PYR_SERIAL: one stream for the pyramid only.
+static sgpyr::Rules pyramid_rules(const sgpu_ctx* ctx, const Part& pt) {
+    const int f = ctx->debug_flags;
+    sgpyr::Rules R;
+    R.kds = ctx->sched.level_ds - ctx->sched.level_min;
+    R.side_stream = !pt.one_stream;
+    R.serial = (f & SGPU_DEBUG_PYR_SERIAL) != 0;
+    R.wave_rows = (f & SGPU_DEBUG_GAUSS_BLOCK) ? -1 : ((f >> SGPU_DEBUG_BAND_SHIFT) & 0x7ff);
+    R.long_bands = (f & SGPU_DEBUG_GAUSS_LONG_BANDS) != 0;
+    R.tiles_off = (f & SGPU_DEBUG_GAUSS_TILE_OFF) != 0;
+    R.tiles_always = (f & SGPU_DEBUG_GAUSS_TILE_ALWAYS) != 0;
+    R.tile_mb = ctx->tile_mb;
+    R.tile_duo = ctx->tile_duo;
+    R.duo_off = (f & SGPU_DEBUG_DUO_OFF) != 0;
+    R.duo_always = (f & SGPU_DEBUG_DUO_ALWAYS) != 0;
+    R.duo_on = ctx->duo_on;
+    R.duo_wide = ctx->duo_wide;
+    R.duo_u8 = ctx->duo_u8;
+    R.trio_mode = ctx->trio_mode;
+    R.duo_plan = ctx->duo_plan;
+    return R;
+}
+static_assert(SGPU_TRIO_OFF == sgpyr::kTrioOff && SGPU_TRIO_ON == sgpyr::kTrioOn &&
+              SGPU_TRIO_ALWAYS == sgpyr::kTrioAlways && SGPU_PAIRS_FRONT == sgpyr::kPairsFront &&
+              SGPU_PAIRS_END == sgpyr::kPairsEnd, "sgpu.h and sift_pyramid_plan.h agree");
+
+// k_gauss_duo's / k_gauss_trio's scratch stores (grow-only, shared by the context's parts)
+static int ensure_gauss_trash(sgpu_ctx* ctx) {
+    ALLOCCHK(ctx, ctx->duo_trash.ensure(std::max(sgk::kGaussDuoTrashBytes, sgk::kGaussTrioTrashBytes)));
+    return SGPU_OK;
+}
+
+// Queue the whole pipeline of one part on its stream.  `wait` (may be null) is an event the
+// part's pyramid must wait for.  No host synchronisation.
+static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32, int stride,
+                        hipEvent_t wait, hipEvent_t wait_lo = nullptr) {
+    hipStream_t st = pt.stream;   // reassigned per stage below
+    const sgpu_options& O = ctx->opt;
+    const int n = pt.n, h = ctx->h;
+    const int rc_layout = layout_part(ctx, pt);
+    if (rc_layout != SGPU_OK) return rc_layout;
+    const sgk::FeatureParams& fp = pt.fp;
+    const long long moff = pt.mask_words;
+    const size_t nc = pt.cand_cap, ne_cap = 2 * nc;
+
+    if (wait) HIPCHK(ctx, hipStreamWaitEvent(st, wait, 0));
+    // stage events: always where a stream waits on them (the multi-stream layouts, the
+    // host-in / host-out stream), else only when the context times its stages
+    pt.events = ctx->stage_timing || !pt.one_stream || ctx->nparts > 1 || ctx->streaming;
+    auto rec = [&](int i, hipStream_t s_) -> hipError_t {
+        return pt.events ? hipEventRecord(pt.ev[i], s_) : hipSuccess;
+    };
+    HIPCHK(ctx, rec(0, st));
+    const size_t img_elems = (size_t)stride * h;
+    const uint8_t* src8 = is_f32 ? nullptr : (const uint8_t*)src_in + (size_t)pt.img0 * img_elems;
+    const float* srcf = is_f32 ? (const float*)src_in + (size_t)pt.img0 * img_elems : nullptr;
+
+    // ---- Gaussian pyramid (BuildPyramid, PyramidCU.cpp:979-1044) for the whole part: the level
+    // filters, the planner's launch list for them (sift_pyramid_plan.h: every schedule decision
+    // is made there), and one launch per entry.
+    float* pyr = pt.pyr.as<float>();
+    const int rc_ops = build_level_ops(ctx, pt, src8, srcf, stride, st);
+    if (rc_ops != SGPU_OK) return rc_ops;
+    const sgpyr::Rules R = pyramid_rules(ctx, pt);
+    sgpyr::plan_pyramid(pt.levels.data(), (int)pt.levels.size(), R, OpSupport{pt.ops.data()}, pt.plan);
+    const int rc_trash = pt.plan.trash ? ensure_gauss_trash(ctx) : SGPU_OK;
+    if (rc_trash != SGPU_OK) return rc_trash;
+    const bool side = pt.plan.side;
+    float* const trash = ctx->duo_trash.as<float>();
+    pt.gauss_launches = 0;   // kernel launches of the level filters (sgpu_last_pyramid_launches)
+    for (const sgpyr::Launch& l : pt.plan.launches) {
+        const hipStream_t s_ = l.side ? pt.stream_oct : st;
+        const sgk::LevelOp& a = pt.ops[l.op[0]];
+        const sgk::LevelOp& b = pt.ops[std::max(l.op[1], 0)];   // (a again where the kind has no b, c)
+        const sgk::LevelOp& c = pt.ops[std::max(l.op[2], 0)];
+        int nl = 1;   // the two-job launchers report 1 or 2
+        if (l.wait_ds) HIPCHK(ctx, hipStreamWaitEvent(s_, pt.ev_ds, 0));
+        switch (l.kind) {
+            case sgpyr::kLevel: HIPCHK(ctx, sgk::launch_gauss_op(a, s_, R.wave_rows, R.long_bands)); break;
+            case sgpyr::kTile: HIPCHK(ctx, sgk::launch_gauss_tile(a, s_)); break;
+            case sgpyr::kTwo: HIPCHK(ctx, sgk::launch_gauss_two(a, b, s_, R.wave_rows, R.long_bands, &nl)); break;
+            case sgpyr::kTileTwo: HIPCHK(ctx, sgk::launch_gauss_tile_two(a, b, s_, &nl)); break;
+            case sgpyr::kTileDuo: HIPCHK(ctx, sgk::launch_gauss_tile_duo(a, b, s_)); break;
+            case sgpyr::kTileDuoOne: HIPCHK(ctx, sgk::launch_gauss_tile_duo_one(a, b, c, s_, &nl)); break;
+            case sgpyr::kDuo:
+                HIPCHK(ctx, sgk::launch_gauss_duo(a, b, s_, R.wave_rows, trash, ctx->duo_strips));
+                break;
+            case sgpyr::kTrio: HIPCHK(ctx, sgk::launch_gauss_trio(a, b, c, s_, R.wave_rows, trash)); break;
+            default: return ctx->fail(SGPU_EINVAL, "unknown pyramid launch kind");
         }
-        int last_launch = 0;
-        for (Job& jb : jobs) {
-            const Op& e = ops[jb.i0];
-            int dep = -1;   // the op writing this job's input level
-            if (e.k >= 2 || (e.k == 1 && e.o == 0)) dep = op_index(e.o, e.k - 1);
-            else if (e.k == 1) dep = op_index(e.o - 1, kds);
-            jb.launch = dep < 0 ? 0 : jobs[job_of[dep]].launch + 1;
-            last_launch = std::max(last_launch, jb.launch);
-        }
-        for (int L = 0; L <= last_launch; L++) {
-            std::vector<const Job*> in;
-            for (const Job& jb : jobs)
-                if (jb.launch == L) in.push_back(&jb);
-            size_t q = 0;
-            if (in.size() == 2 && in[0]->n != in[1]->n) {   // a duo beside a single level
-                const Job* d = in[0]->n == 2 ? in[0] : in[1];
-                const Job* o1 = in[0]->n == 2 ? in[1] : in[0];
-                int nl = 0;
-                HIPCHK(ctx, sgk::launch_gauss_tile_duo_one(ops[d->i0].op, ops[d->i0 + 1].op,
-                                                           ops[o1->i0].op, st, &nl));
-                pt.gauss_launches += nl;
-                q = 2;
-            } else if (in.size() == 2 && in[0]->n == 1 && in[1]->n == 1) {
-                int nl = 0;
-                HIPCHK(ctx, sgk::launch_gauss_tile_two(ops[in[0]->i0].op, ops[in[1]->i0].op, st, &nl));
-                pt.gauss_launches += nl;
-                q = 2;
-            }
-            for (; q < in.size(); q++) {
-                const Job& jb = *in[q];
-                if (jb.n == 2) HIPCHK(ctx, sgk::launch_gauss_tile_duo(ops[jb.i0].op, ops[jb.i0 + 1].op, st));
-                else HIPCHK(ctx, sgk::launch_gauss_tile(ops[jb.i0].op, st));
-                pt.gauss_launches++;
-            }
-        }
-    } else if (side || (ctx->debug_flags & SGPU_DEBUG_PYR_SERIAL) || kds < 1) {
-        // octave by octave, one level per launch (octaves >= 1 on the side stream in the
-        // stream layout)
-        for (const Op& e : ops) {
-            const hipStream_t so = side && e.o >= 1 ? pt.stream_oct : st;
-            pt.gauss_launches++;
-            if (side && e.o == 1 && e.k == 1) HIPCHK(ctx, hipStreamWaitEvent(so, pt.ev_ds, 0));
-            HIPCHK(ctx, level(e.op, so));
-            if (side && e.o == 0 && e.k == kds && e.op.ds_dst) HIPCHK(ctx, hipEventRecord(pt.ev_ds, st));
-        }
-    } else {
-        // Diagonal schedule: op (o, k) in slot o * kds + k.  Its inputs come
-        // from earlier slots -- (o, k-1), and for k = 1 octave o-1's level kds (slot o * kds)
-        // -- so the ops of a slot are independent and share a launch: octave o+1's levels 1, 2
-        // run beside octave o's levels kds+1, kds+2 (15 launches instead of 21 for -no 4 -d 3),
-        // the small jobs' latency-bound waves filling the large ones' CU slots.
-        // Paired levels: ops (o, k) and (o, k+1) of a streaming-size level
-        // (>= SGK_DUO_MIN_MB: not left in the Infinity Cache by the previous launch) with a
-        // compiled width pair run as one k_gauss_duo launch in slot o * kds + k + 1 -- level k
-        // read once, levels k+1 and k+2 written (12 instead of 16 B per pixel).
-        const bool duo_all = (ctx->debug_flags & SGPU_DEBUG_DUO_ALWAYS) != 0;
-        const bool duo_off = (ctx->debug_flags & SGPU_DEBUG_DUO_OFF) != 0 ||
-                             (!SGK_DUO_DEFAULT && !duo_all && !ctx->duo_on);
-        // Three levels: ops (o, k), (o, k+1), (o, k+2) with the widths (11, 13,
-        // 17) and the third decimated into octave o+1 run as one k_gauss_trio launch in slot
-        // o * kds + k + 2 (level k read once, levels k+1 .. k+3 and the decimation written:
-        // 17 instead of 25 B per pixel), on levels >= SGK_TRIO_MIN_MB (any size with
-        // SGPU_TRIO_ALWAYS); the octave's (21, 25) pair after it then pairs too.
-        std::vector<char> trio_third(ops.size(), 0), in_trio(ops.size(), 0);
-        std::vector<char> trio_octave(sgk::kMaxOctaves, 0);
-        if (!duo_off && wave_rows >= 0 && ctx->trio_mode != SGPU_TRIO_OFF) {
-            for (size_t i = 0; i + 2 < ops.size(); i++) {
-                const Op& a = ops[i];
-                const Op& b = ops[i + 1];
-                const Op& c = ops[i + 2];
-                if (in_trio[i] || a.o != b.o || a.o != c.o || b.k != a.k + 1 || c.k != a.k + 2) continue;
-                const long long bytes = 4ll * a.op.w * a.op.h * a.op.batch;
-                if (ctx->trio_mode != SGPU_TRIO_ALWAYS && bytes < ((long long)SGK_TRIO_MIN_MB << 20))
-                    continue;
-                if (!sgk::gauss_trio_supported(a.op, b.op, c.op)) continue;
-                in_trio[i] = in_trio[i + 1] = in_trio[i + 2] = 1;
-                trio_third[i + 2] = 1;
-                trio_octave[a.o] = 1;
-            }
-        }
-        std::vector<int> duo_next(ops.size(), -1);   // op i pairs with op duo_next[i]
-        std::vector<char> duo_second(ops.size(), 0);
-        // Pairs from the octave's end: on a level of >= SGK_DUO_WIDE_MIN_MB (any
-        // size with SGPU_DEBUG_DUO_ALWAYS), octave o's levels pair as (4, 5) = (21, 25), (2, 3) =
-        // (13, 17) with level 3's decimation, (0, 1) = the u8 ingest pair (13, 11) -- three
-        // launches for octave 0 instead of four (level 0, (1, 2), (3, 4), level 5), 34 instead of
-        // 38 B per pixel -- when the (2, 3) pair is supported; otherwise the pairs from the front.
-        if (!duo_off && wave_rows >= 0 && ctx->duo_plan == SGPU_PAIRS_END) {
-            for (size_t j = ops.size(); j >= 2; j--) {
-                const size_t i = j - 2;   // candidate pair (i, i + 1)
-                const Op& a = ops[i];
-                const Op& b = ops[i + 1];
-                if (a.o != b.o || b.k != a.k + 1 || (b.k % 2) != 1) continue;
-                if (in_trio[i] || in_trio[i + 1] || duo_second[i] || duo_next[i + 1] >= 0) continue;
-                const long long bytes = 4ll * a.op.w * a.op.h * a.op.batch;
-                if (!duo_all && (bytes < ((long long)SGK_DUO_WIDE_MIN_MB << 20) ||
-                                 a.op.w > SGK_DUO_PLAN_MAXW))
-                    continue;
-                // the octave takes the plan only with its (2, 3) pair: look it up first
-                bool mid_ok = false;
-                for (size_t q = 0; q + 1 < ops.size(); q++)
-                    if (ops[q].o == a.o && ops[q].k == 2 && ops[q + 1].k == 3 && ops[q + 1].o == a.o)
-                        mid_ok = sgk::gauss_duo_supported(ops[q].op, ops[q + 1].op) &&
-                                 ops[q + 1].op.ds_dst != nullptr;
-                if (!mid_ok || !sgk::gauss_duo_supported(a.op, b.op)) continue;
-                duo_next[i] = (int)(i + 1);
-                duo_second[i + 1] = 1;
-            }
-        }
-        if (!duo_off && wave_rows >= 0) {
-            for (size_t i = 0; i + 1 < ops.size(); i++) {
-                const Op& a = ops[i];
-                const Op& b = ops[i + 1];
-                if (in_trio[i] || in_trio[i + 1]) continue;
-                if (duo_second[i] || duo_next[i] >= 0 || duo_second[i + 1] || duo_next[i + 1] >= 0) continue;
-                if (a.o != b.o || b.k != a.k + 1) continue;
-                const long long bytes = 4ll * a.op.w * a.op.h * a.op.batch;
-                if (!duo_all && bytes < ((long long)SGK_DUO_MIN_MB << 20)) continue;
-                if (!duo_all && a.op.fw + b.op.fw > 24) {
-                    const bool ds_pair = a.op.ds_dst != nullptr;
-                    if (!ds_pair && !ctx->duo_wide && !trio_octave[a.o]) continue;
-                    if (bytes < ((long long)SGK_DUO_WIDE_MIN_MB << 20)) continue;
-                }
-                // the u8 ingest pair (levels 0, 1: 725 us) displaces the (11, 13) pair of levels
-                // 1, 2 (750 us, level 0 alone 390): opt-in
-                if (!duo_all && !ctx->duo_u8 && a.op.src_u8) continue;
-                // (a pair that decimates its second level only in the plan from the octave's end)
-                if (b.op.ds_dst || !sgk::gauss_duo_supported(a.op, b.op)) continue;
-                duo_next[i] = (int)(i + 1);
-                duo_second[i + 1] = 1;
-            }
-        }
-        bool any_duo = false, any_trio = false;
-        for (int v : duo_next) any_duo |= v >= 0;
-        for (char v : trio_third) any_trio |= v != 0;
-        if (any_duo || any_trio)
-            ALLOCCHK(ctx, ctx->duo_trash.ensure(std::max(sgk::kGaussDuoTrashBytes,
-                                                         sgk::kGaussTrioTrashBytes)));
-        int last = 0;
-        for (const Op& e : ops) last = std::max(last, e.o * kds + e.k);
-        for (int slot = 0; slot <= last; slot++) {
-            const sgk::LevelOp* in_slot[sgk::kMaxOctaves];
-            int m = 0;
-            for (size_t i = 0; i < ops.size(); i++) {
-                const Op& e = ops[i];
-                if (trio_third[i] && e.o * kds + e.k == slot) {   // the trio ends in this slot
-                    HIPCHK(ctx, sgk::launch_gauss_trio(ops[i - 2].op, ops[i - 1].op, e.op, st,
-                                                       wave_rows, ctx->duo_trash.as<float>()));
-                    pt.gauss_launches++;
-                } else if (duo_second[i] && e.o * kds + e.k == slot) {   // the pair ends in this slot
-                    HIPCHK(ctx, sgk::launch_gauss_duo(ops[i - 1].op, e.op, st, wave_rows,
-                                                      ctx->duo_trash.as<float>(), ctx->duo_strips));
-                    pt.gauss_launches++;
-                } else if (!in_trio[i] && duo_next[i] < 0 && !duo_second[i] && e.o * kds + e.k == slot) {
-                    in_slot[m++] = &e.op;
-                }
-            }
-            int i = 0;
-            for (; i + 1 < m; i += 2) {
-                int nl = 0;
-                const bool ta = tiled(*in_slot[i]), tb = tiled(*in_slot[i + 1]);
-                if (ta && tb) {
-                    HIPCHK(ctx, sgk::launch_gauss_tile_two(*in_slot[i], *in_slot[i + 1], st, &nl));
-                } else if (!ta && !tb) {
-                    HIPCHK(ctx, sgk::launch_gauss_two(*in_slot[i], *in_slot[i + 1], st, wave_rows,
-                                                      long_bands, &nl));
-                } else {
-                    HIPCHK(ctx, level(*in_slot[i], st));
-                    HIPCHK(ctx, level(*in_slot[i + 1], st));
-                    nl = 2;
-                }
-                pt.gauss_launches += nl;
-            }
-            if (i < m) {
-                HIPCHK(ctx, level(*in_slot[i], st));
-                pt.gauss_launches++;
-            }
-        }
+        pt.gauss_launches += nl;
+        if (l.rec_ds) HIPCHK(ctx, hipEventRecord(pt.ev_ds, st));
     }
     if (side) {
         HIPCHK(ctx, hipEventRecord(pt.ev_oct, pt.stream_oct));
@@ -2486,6 +2304,24 @@ int sgpu_debug_match_plan_stats(const sgpu_ctx* ctx, long long out[4]) {
     out[2] = tiles;
     out[3] = chunks;
     return SGPU_OK;
+}
+
+static_assert(SGPU_PLAN_KINDS == sgpyr::kKinds && SGPU_PLAN_TRIO == sgpyr::kTrio &&
+              SGPU_PLAN_TILE_DUO_ONE == sgpyr::kTileDuoOne, "sgpu.h and sift_pyramid_plan.h agree");
+int sgpu_debug_pyramid_plan(const sgpu_ctx* ctx, int* out, int cap) {
+    if (!ctx || ctx->batch <= 0 || cap < 0 || (cap > 0 && !out)) return SGPU_EINVAL;
+    const Part& pt = ctx->part[0];
+    const int n = (int)pt.plan.launches.size();
+    for (int e = 0; e < n && (e + 1) * SGPU_PLAN_ENTRY_INTS <= cap; e++) {
+        const sgpyr::Launch& l = pt.plan.launches[e];
+        int* p = out + e * SGPU_PLAN_ENTRY_INTS;
+        p[0] = l.kind;
+        for (int j = 0; j < 3; j++) {
+            p[1 + 2 * j] = l.op[j] < 0 ? -1 : pt.levels[l.op[j]].o;
+            p[2 + 2 * j] = l.op[j] < 0 ? -1 : pt.levels[l.op[j]].k;
+        }
+    }
+    return n;
 }
 
 static_assert(SGPU_DUO_STRIPS_RULE == sgk::kDuoStripsRule && SGPU_DUO_STRIPS_WAVE == sgk::kDuoStripsWave &&

@@ -57,6 +57,7 @@
 #include "sift_gauss_coop_plan.h"
 #include "sift_gauss_ring.h"
 #include "sift_kernels.h"
+#include "sift_pyramid_plan.h"
 
 // the DMA asm names M0 as clobbered: clang warns that M0 is reserved; nothing else in this file
 // uses M0 (no builtin LDS-DMA, no indirect register indexing), see duo_wave's dma()
@@ -825,19 +826,16 @@ hipError_t duo_launch(const LevelOp& a, const LevelOp& b, hipStream_t stream, in
 }  // namespace
 
 bool gauss_duo_supported(const LevelOp& a, const LevelOp& b) {
-    // f32 pairs (11, 13), (21, 25), (17, 21) with level k + 1 decimated into the next octave,
-    // (13, 17) with level k + 2 decimated; the u8 ingest pair (13, 11) (level 0 from the image,
-    // level 1)
+    // the compiled width pairs (sgpyr::duo_widths), and where a level is decimated, its geometry
     const bool u8 = a.src_u8 != nullptr;
     const bool ds = a.ds_dst != nullptr, dsb = b.ds_dst != nullptr;
-    const bool dsb_ok = dsb && a.fw == 13 && b.fw == 17 && (b.w % 2) == 0 && b.ds_w * 2 == b.w &&
+    const bool widths = sgpyr::duo_widths(a.fw, b.fw, u8, ds, dsb);
+    const bool dsb_ok = dsb && widths && (b.w % 2) == 0 && b.ds_w * 2 == b.w &&
                         (b.ds_h == (b.h + 1) / 2 || b.ds_h == b.h / 2) &&
                         b.ds_img_stride >= (long long)b.ds_w * b.ds_h;
-    const bool pair = u8 ? (a.fw == 13 && b.fw == 11 && !ds && !dsb)
-                    : dsb ? (dsb_ok && !ds)
-                    : ds ? (a.fw == 17 && b.fw == 21 && (a.w % 2) == 0 && a.ds_w * 2 == a.w &&
-                            a.ds_h == (a.h + 1) / 2 && a.ds_img_stride >= (long long)a.ds_w * a.ds_h)
-                         : ((a.fw == 11 && b.fw == 13) || (a.fw == 21 && b.fw == 25));
+    const bool dsa_ok = (a.w % 2) == 0 && a.ds_w * 2 == a.w && a.ds_h == (a.h + 1) / 2 &&
+                        a.ds_img_stride >= (long long)a.ds_w * a.ds_h;
+    const bool pair = widths && (!dsb || dsb_ok) && (u8 || dsb || !ds || dsa_ok);
     const bool src_ok = u8 ? (!a.src && (a.src_stride % 4) == 0 && (a.src_img_stride % 4) == 0 &&
                               ((uintptr_t)a.src_u8 % 4) == 0)
                            : (a.src && a.src_stride >= a.w);

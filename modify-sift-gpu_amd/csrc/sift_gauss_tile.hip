@@ -24,6 +24,7 @@
 #include <utility>
 
 #include "sift_kernels.h"
+#include "sift_pyramid_plan.h"
 
 namespace sgk {
 namespace {
@@ -567,16 +568,13 @@ namespace sgk {
 // (11, 13) and (17, 21) for other pairings).
 bool gauss_tile_duo_supported(const LevelOp& a, const LevelOp& b) {
     if (!gauss_tile_supported(a) || !gauss_tile_supported(b)) return false;
-    if (a.ds_dst || b.src_u8 || (b.zero.n[0] | b.zero.n[1] | b.zero.n[2])) return false;
-    if (a.src_u8 && b.ds_dst) return false;
+    if (b.src_u8 || (b.zero.n[0] | b.zero.n[1] | b.zero.n[2])) return false;
     const bool geo = b.src == a.dst && a.w == b.w && a.h == b.h && a.batch == b.batch &&
                      b.src_stride == a.w && a.dst_img_stride == b.dst_img_stride &&
                      b.src_img_stride == a.dst_img_stride && a.dst_img_stride >= (long long)a.w * a.h;
     if (!geo) return false;
-    const int fa = a.fw, fb = b.fw;
-    if (b.ds_dst) return fa == 13 && fb == 17;
-    return (fa == 13 && fb == 11) || (fa == 13 && fb == 17) || (fa == 21 && fb == 25) ||
-           (fa == 11 && fb == 13) || (fa == 17 && fb == 21);
+    return sgpyr::tile_duo_widths(a.fw, b.fw, a.src_u8 != nullptr, a.ds_dst != nullptr,
+                                  b.ds_dst != nullptr);
 }
 
 hipError_t launch_gauss_tile_duo(const LevelOp& a, const LevelOp& b, hipStream_t stream) {

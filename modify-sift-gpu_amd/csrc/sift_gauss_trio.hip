@@ -36,6 +36,7 @@
 
 #include "sift_gauss_ring.h"
 #include "sift_kernels.h"
+#include "sift_pyramid_plan.h"
 
 // the DMA asm names M0 as clobbered (gring::dma_pair5): clang warns that M0 is reserved; nothing
 // else in this file uses M0
@@ -564,7 +565,7 @@ hipError_t trio_launch(const LevelOp& a, const LevelOp& b, const LevelOp& c, hip
 bool gauss_trio_supported(const LevelOp& a, const LevelOp& b, const LevelOp& c) {
     // f32 levels k -> k+1 -> k+2 -> k+3 with widths (11, 13, 17) and level k+3 decimated into the
     // next octave's level 0
-    const bool widths = a.fw == 11 && b.fw == 13 && c.fw == 17;
+    const bool widths = sgpyr::trio_widths(a.fw, b.fw, c.fw);
     const bool ds = c.ds_dst && (a.w % 2) == 0 && c.ds_w * 2 == a.w &&
                     (c.ds_h == (a.h + 1) / 2 || c.ds_h == a.h / 2) &&
                     c.ds_img_stride >= (long long)c.ds_w * c.ds_h;

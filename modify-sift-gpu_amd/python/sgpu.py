@@ -36,8 +36,11 @@ C_API = [
     "sgpu_set_host_output", "sgpu_debug_set_schedule", "sgpu_debug_set_match_prune",
     "sgpu_quantize_descriptors_gpu", "sgpu_feature_descriptors_u8", "sgpu_copy_features_u8",
     "sgpu_match_batch", "sgpu_match_images", "sgpu_debug_match_plan_stats",
-    "sgpu_debug_set_duo_strips",
+    "sgpu_debug_set_duo_strips", "sgpu_debug_pyramid_plan",
 ]
+
+# launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
+PLAN_KINDS = ("level", "tile", "two", "tile_two", "tile_duo", "tile_duo_one", "duo", "trio")
 
 _LIB = None
 
@@ -114,6 +117,7 @@ def lib():
         L.sgpu_match_images.argtypes = [vp, vp, c.c_int, c.c_float, c.c_float, c.c_int, c.c_int,
                                         vp, c.c_int64, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
+        L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
     return _LIB
 
@@ -250,6 +254,19 @@ class SiftContext:
         if n < 0:
             raise RuntimeError("sgpu_last_pyramid_launches: no extract")
         return int(n), int(f.value)
+
+    def pyramid_plan(self):
+        """The launch list of the last extract's Gaussian pyramid (sgpu_debug_pyramid_plan), in
+        issue order: a list of (kind, levels) with kind one of PLAN_KINDS and levels the (octave,
+        level written) of each level filter the launch runs."""
+        n = lib().sgpu_debug_pyramid_plan(self._ctx, None, 0)
+        if n < 0:
+            raise RuntimeError("sgpu_debug_pyramid_plan: no extract")
+        out = np.zeros((n, 7), np.int32)
+        self._check(min(0, lib().sgpu_debug_pyramid_plan(self._ctx, out.ctypes.data, out.size)),
+                    "sgpu_debug_pyramid_plan")
+        return [(PLAN_KINDS[int(e[0])], [(int(e[1 + 2 * j]), int(e[2 + 2 * j]))
+                                         for j in range(3) if e[1 + 2 * j] >= 0]) for e in out]
 
     def set_stage_timing(self, on: bool):
         """Per-stage HIP events on/off (sgpu_set_stage_timing; the reference's _timingS)."""
