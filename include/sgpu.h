@@ -265,6 +265,36 @@ int sgpu_match_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, float d
                       float ratiomax, int mutual_best_match, int max_match,
                       int* out_pairs, int64_t cap, int* out_counts);
 
+/* Guided matching of many set pairs in one call, each pair under its own matrices: pair p =
+ * (a, b) gives exactly sgpu_match_guided(set a, set b, loc a, loc b, H + 9 p, F + 9 p, ...), set
+ * a being the reference's set 1 (H x1 is compared with x2; the 8-row block rule of
+ * MultiplyDescriptorG_Kernel counts set a's rows from the set's first row).  loc is
+ * [set_offsets[nsets]][2] floats (x, y), packed, host or device memory together with desc
+ * (SGPU_INPUT_DEVICE covers both); H and F are host arrays [npairs][9], row-major 3x3, or NULL:
+ * a missing array is the identity with its threshold at 1e20 for every pair.  Both NULL: the call
+ * is sgpu_match_batch and loc may be NULL.  Outputs, cap / SGPU_ERANGE, max_match, the legal
+ * pair lists, SGPU_EINVAL and times[8] are sgpu_match_batch's; SGPU_EINVAL also for a NULL loc
+ * with a matrix.  The geometric test runs inside the matching kernel: no mask is stored, and the
+ * number of launches, copies and synchronisations does not depend on npairs (the matrices go up
+ * with the plan's tables). */
+int sgpu_match_batch_guided(sgpu_ctx* ctx, const uint8_t* desc, const float* loc,
+                            const int64_t* set_offsets, int nsets,
+                            const int* set_pairs /* [npairs][2] */, int npairs,
+                            const float* H /* [npairs][9] or NULL */,
+                            const float* F /* [npairs][9] or NULL */,
+                            float distmax, float ratiomax, float hdistmax, float fdistmax,
+                            int mutual_best_match, int max_match,
+                            int* out_pairs /* [cap][2] */, int64_t cap,
+                            int* out_counts /* [npairs] */, int flags);
+/* sgpu_match_batch_guided over the last extract: descriptors as sgpu_match_images, locations =
+ * x, y of the batch's device keys (the two floats SetFeatureLocation takes with gap = 2), so
+ * neither a key nor a descriptor crosses PCIe.  Error conditions of sgpu_match_images. */
+int sgpu_match_images_guided(sgpu_ctx* ctx, const int* image_pairs, int npairs,
+                             const float* H, const float* F,
+                             float distmax, float ratiomax, float hdistmax, float fdistmax,
+                             int mutual_best_match, int max_match,
+                             int* out_pairs, int64_t cap, int* out_counts);
+
 /* Timing of the last call: stage times in milliseconds measured with HIP events
  * (SiftGPU::_timing, SiftPyramid.cpp:48-56).  times[0..7] =
  * {upload, pyramid, detect, orientation, expand, descriptor, download, total} of the last

@@ -198,6 +198,7 @@ struct sgpu_ctx {
     // grouped pair matcher (sgpu_match_batch): uploaded descriptors and their s8 form / row sums,
     // the planner's tables, chunk partials, decisions, [counts npairs][offsets npairs + 1], pairs
     DevBuf b_desc, b_s8, b_sums, b_plan, b_part, b_dec, b_cnt, b_out;
+    DevBuf b_loc;                          // sgpu_match_batch_guided: uploaded locations [rows][2]
     sgplan::Plan b_hplan;
     bool b_planned = false;                // b_hplan is a call's plan (sgpu_debug_match_plan_stats)
     std::vector<unsigned char> b_tables;   // the tables as uploaded (alive until the call's sync)
@@ -519,7 +520,7 @@ int sgpu_ctx_destroy(sgpu_ctx* ctx) {
                       &ctx->m_part, &ctx->m_terms, &ctx->m_match, &ctx->m_dist, &ctx->m_mask, &ctx->m_loc,
                       &ctx->m_colpart, &ctx->m_cols, &ctx->m_prune, &ctx->m_s1c,
                       &ctx->b_desc, &ctx->b_s8, &ctx->b_sums, &ctx->b_plan, &ctx->b_part, &ctx->b_dec,
-                      &ctx->b_cnt, &ctx->b_out, &ctx->q_in, &ctx->q_out, &ctx->f_u8, &ctx->f_s8,
+                      &ctx->b_cnt, &ctx->b_out, &ctx->b_loc, &ctx->q_in, &ctx->q_out, &ctx->f_u8, &ctx->f_s8,
                       &ctx->f_sums, &ctx->c_buf};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i <= T_N; i++)
@@ -2131,10 +2132,22 @@ int sgpu_copy_features_u8(sgpu_ctx* ctx, int image, uint8_t* desc) {
 // their matcher forms when the caller has them (sgpu_match_images), else derived here in one
 // launch.  One table upload, six launches, two device->host copies and two
 // synchronisations, whatever npairs is.
+// Guided (geo.H or geo.F set): the work items run k_match_pairs_guided over the device locations
+// geo.loc; the pairs' matrices (a missing one: the identity, threshold 1e20, SiftMatch.cpp:
+// 667-675) follow the plan's tables in the same upload.  Nothing else changes.
+struct BatchGeometry {
+    const float* loc = nullptr;   // device: x, y of row r at loc[r * stride]
+    int stride = 2;
+    const float* H = nullptr;     // host [npairs][9] or null
+    const float* F = nullptr;
+    float hdistmax = 0.f, fdistmax = 0.f;
+};
 static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8, const int* sums,
                             const int64_t* off, int nsets, const int* set_pairs, int npairs,
                             float distmax, float ratiomax, int mbm, int max_match, int* out_pairs,
-                            int64_t cap, int* out_counts, bool timing_started = false) {
+                            int64_t cap, int* out_counts, bool timing_started = false,
+                            const BatchGeometry& geo = BatchGeometry{}) {
+    const bool guided = geo.H || geo.F;
     hipStream_t st = ctx->stream;
     sgplan::Plan& plan = ctx->b_hplan;
     const int prc = sgplan::build_plan(off, nsets, set_pairs, npairs, mbm != 0, max_match, plan);
@@ -2153,6 +2166,7 @@ static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8,
         return 0;
     }
     if (!u8) return ctx->fail(SGPU_EINVAL, "null descriptors");
+    if (guided && !geo.loc) return ctx->fail(SGPU_EINVAL, "guided match needs locations");
     if (!ctx->dist_ready) {
         // the same expression as RowMatch_Kernel (ProgramCU.cu:1838), evaluated on the host
         std::vector<float> t(sgk::kDistTable);
@@ -2163,16 +2177,28 @@ static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8,
         ctx->dist_ready = true;
     }
     // the tables in one buffer, one upload: [items][sides][finish panels][pairs]
+    // (guided: [geometry of every pair])
     const size_t b_items = plan.items.size() * sizeof(sgplan::Item);
     const size_t b_sides = plan.sides.size() * sizeof(sgplan::Side);
     const size_t b_fp = plan.fpanels.size() * sizeof(sgplan::FinishPanel);
     const size_t b_pairs = plan.pairs.size() * sizeof(sgplan::PairRec);
-    ctx->b_tables.resize(b_items + b_sides + b_fp + b_pairs);
+    const size_t b_geom = guided ? (size_t)npairs * sizeof(sgk::GuidedParams) : 0;
+    ctx->b_tables.resize(b_items + b_sides + b_fp + b_pairs + b_geom);
     unsigned char* tb = ctx->b_tables.data();
     memcpy(tb, plan.items.data(), b_items);
     memcpy(tb + b_items, plan.sides.data(), b_sides);
     memcpy(tb + b_items + b_sides, plan.fpanels.data(), b_fp);
     memcpy(tb + b_items + b_sides + b_fp, plan.pairs.data(), b_pairs);
+    if (guided) {
+        static const float kIdentity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        auto* g = reinterpret_cast<sgk::GuidedParams*>(tb + b_items + b_sides + b_fp + b_pairs);
+        for (int p = 0; p < npairs; p++) {
+            memcpy(g[p].H, geo.H ? geo.H + 9 * (size_t)p : kIdentity, sizeof(g[p].H));
+            memcpy(g[p].F, geo.F ? geo.F + 9 * (size_t)p : kIdentity, sizeof(g[p].F));
+            g[p].hdistmax = geo.H ? geo.hdistmax : 1.0e+20f;
+            g[p].fdistmax = geo.F ? geo.fdistmax : 1.0e+20f;
+        }
+    }
     const int64_t out_rows = std::min<int64_t>(cap, plan.out_bound);
     ALLOCCHK(ctx, ctx->b_plan.ensure(ctx->b_tables.size()));
     ALLOCCHK(ctx, ctx->b_part.ensure((size_t)plan.part_total * sizeof(sgk::Top2)));
@@ -2190,6 +2216,8 @@ static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8,
     const auto* d_sides = reinterpret_cast<const sgplan::Side*>(dt + b_items);
     const auto* d_fp = reinterpret_cast<const sgplan::FinishPanel*>(dt + b_items + b_sides);
     const auto* d_pairs = reinterpret_cast<const sgplan::PairRec*>(dt + b_items + b_sides + b_fp);
+    const auto* d_geom =
+        reinterpret_cast<const sgk::GuidedParams*>(dt + b_items + b_sides + b_fp + b_pairs);
     long long* d_offs = ctx->b_cnt.as<long long>();
     int* d_counts = reinterpret_cast<int*>(d_offs + npairs + 1);
     if (!timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
@@ -2199,8 +2227,13 @@ static int match_batch_impl(sgpu_ctx* ctx, const uint8_t* u8, const uint8_t* s8,
         s8 = ctx->b_s8.as<uint8_t>();
         sums = ctx->b_sums.as<int>();
     }
-    HIPCHK(ctx, sgk::launch_match_pairs(s8, d_items, (int)plan.items.size(),
-                                        ctx->b_part.as<sgk::Top2>(), st));
+    if (guided)
+        HIPCHK(ctx, sgk::launch_match_pairs_guided(s8, d_items, (int)plan.items.size(),
+                                                   ctx->b_part.as<sgk::Top2>(), geo.loc, geo.stride,
+                                                   d_geom, st));
+    else
+        HIPCHK(ctx, sgk::launch_match_pairs(s8, d_items, (int)plan.items.size(),
+                                            ctx->b_part.as<sgk::Top2>(), st));
     HIPCHK(ctx, sgk::launch_match_pairs_finish(ctx->b_part.as<sgk::Top2>(), d_sides, d_fp,
                                                (int)plan.fpanels.size(), sums,
                                                ctx->m_dist.as<float>(), distmax, ratiomax,
@@ -2272,6 +2305,77 @@ int sgpu_match_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, float d
                             ctx->f_sums.as<int>(), ctx->img_off.data(), ctx->batch, image_pairs,
                             npairs, distmax, ratiomax, mutual_best_match, max_match, out_pairs, cap,
                             out_counts, quantises);
+}
+
+int sgpu_match_batch_guided(sgpu_ctx* ctx, const uint8_t* desc, const float* loc,
+                            const int64_t* set_offsets, int nsets, const int* set_pairs,
+                            int npairs, const float* H, const float* F, float distmax,
+                            float ratiomax, float hdistmax, float fdistmax, int mutual_best_match,
+                            int max_match, int* out_pairs, int64_t cap, int* out_counts, int flags) {
+    if (!H && !F)
+        return sgpu_match_batch(ctx, desc, set_offsets, nsets, set_pairs, npairs, distmax, ratiomax,
+                                mutual_best_match, max_match, out_pairs, cap, out_counts, flags);
+    if (!ctx) return SGPU_EINVAL;
+    if (nsets < 0 || npairs < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad match batch arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint8_t* u8 = desc;
+    BatchGeometry geo;
+    geo.loc = loc;
+    geo.H = H;
+    geo.F = F;
+    geo.hdistmax = hdistmax;
+    geo.fdistmax = fdistmax;
+    if (!(flags & SGPU_INPUT_DEVICE) && npairs > 0) {
+        // validated offsets before any size is taken from them
+        sgplan::Plan probe;
+        if (sgplan::build_plan(set_offsets, nsets, nullptr, 0, false, 0, probe) != sgplan::kPlanOk)
+            return ctx->fail(SGPU_EINVAL, "bad set offsets");
+        const int64_t total_rows = set_offsets[nsets];
+        if (total_rows > 0) {
+            if (!desc) return ctx->fail(SGPU_EINVAL, "null descriptors");
+            if (!loc) return ctx->fail(SGPU_EINVAL, "guided match needs locations");
+            ALLOCCHK(ctx, ctx->b_desc.ensure((size_t)total_rows * 128));
+            ALLOCCHK(ctx, ctx->b_loc.ensure((size_t)total_rows * 2 * sizeof(float)));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->b_desc.p, desc, (size_t)total_rows * 128,
+                                       hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->b_loc.p, loc, (size_t)total_rows * 2 * sizeof(float),
+                                       hipMemcpyHostToDevice, ctx->stream));
+            u8 = ctx->b_desc.as<uint8_t>();
+            geo.loc = ctx->b_loc.as<float>();
+        }
+    }
+    return match_batch_impl(ctx, u8, nullptr, nullptr, set_offsets, nsets, set_pairs, npairs, distmax,
+                            ratiomax, mutual_best_match, max_match, out_pairs, cap, out_counts, false,
+                            geo);
+}
+
+int sgpu_match_images_guided(sgpu_ctx* ctx, const int* image_pairs, int npairs, const float* H,
+                             const float* F, float distmax, float ratiomax, float hdistmax,
+                             float fdistmax, int mutual_best_match, int max_match, int* out_pairs,
+                             int64_t cap, int* out_counts) {
+    if (!H && !F)
+        return sgpu_match_images(ctx, image_pairs, npairs, distmax, ratiomax, mutual_best_match,
+                                 max_match, out_pairs, cap, out_counts);
+    if (!ctx) return SGPU_EINVAL;
+    if (npairs < 0) return ctx->fail(SGPU_EINVAL, "bad match arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const bool quantises = !ctx->f_ready;
+    if (quantises) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    int rc = feature_u8(ctx);
+    if (rc != SGPU_OK) return rc;
+    // the batch's device keys [x, y, scale, orientation]: the locations are their first two floats
+    BatchGeometry geo;
+    rc = sgpu_device_features(ctx, &geo.loc, nullptr, nullptr);
+    if (rc != SGPU_OK) return rc;
+    geo.stride = 4;
+    geo.H = H;
+    geo.F = F;
+    geo.hdistmax = hdistmax;
+    geo.fdistmax = fdistmax;
+    return match_batch_impl(ctx, ctx->f_u8.as<uint8_t>(), ctx->f_s8.as<uint8_t>(),
+                            ctx->f_sums.as<int>(), ctx->img_off.data(), ctx->batch, image_pairs,
+                            npairs, distmax, ratiomax, mutual_best_match, max_match, out_pairs, cap,
+                            out_counts, quantises, geo);
 }
 
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n) {

@@ -364,6 +364,13 @@ hipError_t launch_quantize_desc(const float* d, size_t n, uint8_t* u8, uint8_t* 
 // of all sets: part[item.part_base + row] = the row's top-2 over the chunk (dot - row term).
 hipError_t launch_match_pairs(const uint8_t* s8, const sgplan::Item* items, int nitems, Top2* part,
                               hipStream_t stream);
+// The guided form: every value carries the geometric bias of MultiplyDescriptorG_Kernel under the
+// matrices of its pair, geom[item.pair] (both matrices filled in); the test runs inside the work
+// item, no mask is stored.  loc = the sets' locations, row r of the buffer at loc[r * loc_stride]
+// (x, y; loc_stride 2 for packed locations, 4 for extracted keys).
+hipError_t launch_match_pairs_guided(const uint8_t* s8, const sgplan::Item* items, int nitems,
+                                     Top2* part, const float* loc, int loc_stride,
+                                     const GuidedParams* geom, hipStream_t stream);
 // One workgroup per (side, panel): merge the side's chunks, add the row term sums[a_off + row],
 // apply distmax / ratiomax -> dec[side.dec_off + row] = matched column of B or -1.
 hipError_t launch_match_pairs_finish(const Top2* part, const sgplan::Side* sides,

@@ -23,6 +23,13 @@
 // the next set's.  A column past the item's chunk is never computed from loaded bytes: its staged
 // bytes are zero and its column term is kNegCol (it can neither win nor raise a second maximum);
 // the staging load itself is clamped to the set's last row, so no load leaves the set either.
+//
+// Guided form (sgpu_match_batch_guided / sgpu_match_images_guided): k_match_pairs_guided is the
+// same work item with the geometric test of MultiplyDescriptorG_Kernel fused in.  Every tile the
+// workgroup evaluates the test for its own 128 x 128 point pairs into an LDS bit matrix
+// (guided_words, the booleans of oracle::guided_pass and k_guided_mask) under its pair's
+// matrices geom[Item::pair], and the accumulators start at the column term minus the geometric
+// bias, as k_match_rows<GUIDED> does -- no mask is stored in device memory.
 #include <algorithm>
 #include <type_traits>
 
@@ -45,6 +52,15 @@ constexpr int kNeg = INT_MIN;
 // the row term >= 0 added in the finish it can neither win nor raise a second maximum, and
 // (acc << 7) does not overflow.
 constexpr int kNegCol = -(1 << 22);
+// Guided form: a value's accumulator starts at the column term minus 2^18 * fail + 2^23 * !good
+// (sift_match.hip, k_match_rows), so acc = dot - row term - bias with dot in [0, 128 * 255^2]
+// (< 2^23), the row term in [0, 128 * 128 * 255] (< 2^22) and the bias in {0, 2^18, 2^23,
+// 2^23 + 2^18}: acc lies in [-2^22 - 2^23 - 2^18, 2^23) = [-12845056, 8388608).  Every partial
+// sum of the MFMA chain obeys the same bounds (|dot of s8 forms| <= 2^21, the column term in
+// [-2^21, 2^21), a missing column's kNegCol with zero bytes), so |acc| < 2^24 and (acc << 7)
+// plus the 7 tie bits fits int32 with INT_MIN still below every key.
+constexpr int kBiasFail = 1 << 18, kBiasNoGood = 1 << 23;
+constexpr int kPassPitch = 5;    // words per LDS bit row (4 + 1 against bank conflicts)
 
 // the median of three as min / max, which LLVM selects as one v_med3_i32 (compiler-visible, so
 // the hazard recognizer sees the MFMA result it reads): with s <= m, med3(s, m, v) is the new
@@ -100,13 +116,82 @@ __global__ __launch_bounds__(256) void k_quantize_desc(const float4* __restrict_
     }
 }
 
+// The geometric test of one set-1 point (x1, y1) -- this thread's -- against 64 points of set 2,
+// shared by both directions: bit k of w[q] = the pair passes with set-2 point base2 + q * 32 + k
+// (MultiplyDescriptorG_Kernel, ProgramCU.cu:1648-1681, in the operation order of
+// oracle::guided_pass and k_guided_mask: explicit fmaf's, a * (1 / b) for the divisions, the
+// Sampson error only where the homography test passed; |a - b| = |b - a| exactly).  Direction 0:
+// set 1 = the panel's rows, set 2 = the tile's columns; direction 1 (A = set b): set 1 = the
+// tile's columns, set 2 = the panel's rows.  set2 = the locations of set 2 (its row 0), n2 its
+// size and lim2 the first point that takes no part (the chunk's or the set's end): a load past
+// the set is clamped to its last point and its bit is cleared.  base2 is uniform over the wave,
+// so the set-2 loads are scalar loads (one per point and wave, none through LDS).
+__device__ __forceinline__ void guided_words(const GuidedParams& gp, float x1, float y1, bool valid1,
+                                             const float* __restrict__ set2, int loc_stride,
+                                             int n2, int lim2, int base2, uint32_t w[2]) {
+    const float* H = gp.H;
+    const float* F = gp.F;
+    const float h0 = __builtin_fmaf(H[0], x1, __builtin_fmaf(H[1], y1, H[2]));
+    const float h1 = __builtin_fmaf(H[3], x1, __builtin_fmaf(H[4], y1, H[5]));
+    const float h2 = __builtin_fmaf(H[6], x1, __builtin_fmaf(H[7], y1, H[8]));
+    const float rh = 1.0f / h2;
+    const float u = h0 * rh, v = h1 * rh;
+    auto point2 = [&](int j) {
+        return *reinterpret_cast<const float2*>(set2 + (size_t)min(j, n2 - 1) * loc_stride);
+    };
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int j0 = base2 + q * 32;
+        uint32_t bits = 0;
+        // branch-free: a short-circuit '&&' compiles to a branch per pair.  All 64 points
+        // unrolled: their scalar loads are issued together (some scalar registers spill to
+        // lanes); batches of 16 points spill none but expose each batch's load latency and
+        // measured 16 % slower on the shard's pairs.
+#pragma unroll
+        for (int k = 0; k < 32; k++) {
+            const float2 p2 = point2(j0 + k);
+            const bool ok = (__builtin_fabsf(u - p2.x) < gp.hdistmax) &
+                            (__builtin_fabsf(v - p2.y) < gp.hdistmax);
+            bits |= (uint32_t)ok << k;
+        }
+        const int nvalid = min(max(lim2 - j0, 0), 32);
+        w[q] = valid1 ? bits & (nvalid == 32 ? 0xffffffffu : ((1u << nvalid) - 1u)) : 0u;
+    }
+    if (w[0] | w[1]) {
+        const float f0 = __builtin_fmaf(F[0], x1, __builtin_fmaf(F[1], y1, F[2]));
+        const float f1 = __builtin_fmaf(F[3], x1, __builtin_fmaf(F[4], y1, F[5]));
+        const float f2 = __builtin_fmaf(F[6], x1, __builtin_fmaf(F[7], y1, F[8]));
+        const float d0 = __builtin_fmaf(f1, f1, f0 * f0);
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            for (uint32_t rest = w[q]; rest; rest &= rest - 1) {
+                const int jj = __builtin_ctz(rest);
+                const float2 p2 = point2(base2 + q * 32 + jj);
+                const float t0 = __builtin_fmaf(F[0], p2.x, __builtin_fmaf(F[3], p2.y, F[6]));
+                const float t1 = __builtin_fmaf(F[1], p2.x, __builtin_fmaf(F[4], p2.y, F[7]));
+                const float x2fx1 = __builtin_fmaf(p2.x, f0, __builtin_fmaf(p2.y, f1, f2));
+                const float den = __builtin_fmaf(t1, t1, __builtin_fmaf(t0, t0, d0));
+                const float se = (x2fx1 * x2fx1) * (1.0f / den);
+                if (!(se < gp.fdistmax)) w[q] &= ~(1u << jj);
+            }
+        }
+    }
+}
+
 // One work item: a 128-row panel of set A against columns [c_begin, c_end) of set B, both sets of
 // the s8 buffer S.  part[part_base + row] = the running top-2 of the row over those columns (dot
 // without the row term).  Fragment layout, staging, keys and the tile bookkeeping are
 // k_match_rows's plain keyed path; the tie order is the item's (tie32 = direction 0).
-__global__ __launch_bounds__(256) void k_match_pairs(const uint8_t* __restrict__ S,
-                                                     const sgplan::Item* __restrict__ items,
-                                                     Top2* __restrict__ part) {
+//
+// GUIDED: loc = the sets' locations (x, y of row r at loc[r * loc_stride]), geom = the pairs'
+// matrices and thresholds, s_pass / s_good = the tile's bit matrices (see guided_words).
+template <bool GUIDED>
+__device__ __forceinline__ void match_pairs_item(const uint8_t* __restrict__ S,
+                                                 const sgplan::Item* __restrict__ items,
+                                                 Top2* __restrict__ part,
+                                                 const float* __restrict__ loc, int loc_stride,
+                                                 const GuidedParams* __restrict__ geom,
+                                                 uint32_t* s_pass, uint32_t* s_good) {
     __shared__ __attribute__((aligned(16))) uint8_t s_b[2][kTile * kLdsRow];
     __shared__ int s_ct[2][kTile];   // column terms of the staged tile (from its bytes)
     const sgplan::Item it = items[blockIdx.x];
@@ -141,6 +226,21 @@ __global__ __launch_bounds__(256) void k_match_pairs(const uint8_t* __restrict__
         for (int i = 0; i < 4; i++) { M[rb][i] = kNeg; S2[rb][i] = kNeg; I[rb][i] = -1; W[rb][i] = 0; }
     const uint32_t prefix = tie32 ? 4u : 128u;   // keys differing below this bit tie
 
+    // guided: of the tile's 128 x 128 point pairs, thread t tests set-1 point t & 127 against the
+    // 64 set-2 points of half t >> 7 (uniform over a wave).  Direction 0: set 1 = the panel's rows
+    // (one location per thread and item); direction 1: set 1 = the tile's columns (the next
+    // tile's location is loaded with its bytes, clamped to the set like them).
+    const int p1 = tid & 127;
+    const int half2 = GUIDED ? __builtin_amdgcn_readfirstlane(tid >> 7) * 64 : 0;
+    const float* __restrict__ locA = GUIDED ? loc + (size_t)it.a_off * loc_stride : nullptr;
+    const float* __restrict__ locB = GUIDED ? loc + (size_t)it.b_off * loc_stride : nullptr;
+    const GuidedParams* __restrict__ gp = GUIDED ? geom + it.pair : nullptr;
+    float2 l1row = make_float2(0.f, 0.f), l1next = l1row;
+    if constexpr (GUIDED) {
+        if (tie32)
+            l1row = *reinterpret_cast<const float2*>(locA + (size_t)min(panel * kPanel + p1, nA - 1) * loc_stride);
+    }
+
     // staging: thread t copies 64 bytes: column t>>1, half (t&1).  The loads are unconditional
     // and clamped to the set's last row (never the next set's bytes, never past the buffer);
     // stage_store zeroes the columns past the chunk.
@@ -149,6 +249,10 @@ __global__ __launch_bounds__(256) void k_match_pairs(const uint8_t* __restrict__
         const uint8_t* src = B + (size_t)col * 128 + (tid & 1) * 64;
 #pragma unroll
         for (int q = 0; q < 4; q++) r[q] = reinterpret_cast<const uint4*>(src)[q];
+        if constexpr (GUIDED) {
+            if (!tie32)
+                l1next = *reinterpret_cast<const float2*>(locB + (size_t)min(tbase + p1, nB - 1) * loc_stride);
+        }
     };
     // the column term 128 * sum(u8 B[col]) - 2^21 from the staged s8 bytes (sum(u) = sum(s) +
     // 128 * 128; v_dot4_i32_i8, the two half-columns joined by one shuffle)
@@ -186,21 +290,92 @@ __global__ __launch_bounds__(256) void k_match_pairs(const uint8_t* __restrict__
     auto tile = [&](auto par, int tb) {
         constexpr int buf = decltype(par)::value;
         const bool has_next = tb + kTile < c_end;
+        const float2 l1 = tie32 ? l1row : l1next;   // (guided: this tile's set-1 location)
         stage_load(tb + kTile, stg);
+        // guided: this tile's geometric test.  s_pass[set-1 point][word of set-2 points] as
+        // k_guided_mask's; s_good[8-point block of set 1][word] = some point of the block
+        // passes (good_count > 0: the blocks count from the set's first row -- panels, chunks and
+        // tiles all start at multiples of 128 -- and a set-1 point past the set does not pass).
+        // rec = this lane's 16-byte record of k_match_rows<GUIDED>: byte rb * 8 + cb covers rows
+        // wave*32 + rb*16 + quad*4 + i and column cb*16 + l16; bit i = the pair fails, bit 4 + i =
+        // no point of its set-1 block passes.  The writes of the next tile wait for this tile's
+        // closing barrier, so every read of this tile's bits is over by then.
+        uint32_t rec[4] = {0, 0, 0, 0};
+        if constexpr (GUIDED) {
+            uint32_t w[2];
+            guided_words(*gp, l1.x, l1.y, tie32 ? panel * kPanel + p1 < nA : tb + p1 < c_end,
+                         tie32 ? locB : locA, loc_stride, tie32 ? nB : nA, tie32 ? c_end : nA,
+                         (tie32 ? tb : panel * kPanel) + half2, w);
+            s_pass[p1 * kPassPitch + (half2 >> 5)] = w[0];
+            s_pass[p1 * kPassPitch + (half2 >> 5) + 1] = w[1];
+            __syncthreads();
+            if (tid < 64) {
+                const int blk = tid >> 2, wd = tid & 3;
+                uint32_t g = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) g |= s_pass[(blk * 8 + k) * kPassPitch + wd];
+                s_good[blk * kPassPitch + wd] = g;
+            }
+            __syncthreads();
+            if (tie32) {
+                // set 1 = the rows, set 2 = the columns
+#pragma unroll
+                for (int rb = 0; rb < 2; rb++) {
+                    const int row0 = wave * 32 + rb * 16 + quad * 4;
+#pragma unroll
+                    for (int cb = 0; cb < 8; cb++) {
+                        const int col = cb * 16 + l16, wd = col >> 5, bit = col & 31;
+                        uint32_t byte = ((s_good[(row0 >> 3) * kPassPitch + wd] >> bit) & 1u) ? 0u : 0xf0u;
+#pragma unroll
+                        for (int i = 0; i < 4; i++)
+                            byte |= (((s_pass[(row0 + i) * kPassPitch + wd] >> bit) & 1u) ^ 1u) << i;
+                        rec[rb * 2 + (cb >> 2)] |= byte << ((cb & 3) * 8);
+                    }
+                }
+            } else {
+                // set 1 = the columns, set 2 = the rows (word `wave` holds this wave's 32 rows)
+#pragma unroll
+                for (int cb = 0; cb < 8; cb++) {
+                    const int c = cb * 16 + l16;
+                    const uint32_t pw = s_pass[c * kPassPitch + wave];
+                    const uint32_t gw = s_good[(c >> 3) * kPassPitch + wave];
+#pragma unroll
+                    for (int rb = 0; rb < 2; rb++) {
+                        const int sh = rb * 16 + quad * 4;
+                        const uint32_t byte = (~(pw >> sh) & 0xfu) | ((~(gw >> sh) & 0xfu) << 4);
+                        rec[rb * 2 + (cb >> 2)] |= byte << ((cb & 3) * 8);
+                    }
+                }
+            }
+        }
         int mt[2][4], st[2][4];
 #pragma unroll
         for (int rb = 0; rb < 2; rb++)
 #pragma unroll
             for (int i = 0; i < 4; i++) { mt[rb][i] = M[rb][i]; st[rb][i] = S2[rb][i]; }
         // the accumulators start at 0 and the column term enters the key,
-        // key = (acc << 7) + ((ct << 7) | low) = ((acc + ct) << 7) | low
+        // key = (acc << 7) + ((ct << 7) | low) = ((acc + ct) << 7) | low;
+        // guided: they start at the column term minus the geometric bias and the key adds only
+        // the tie bits (the range of acc: kBiasFail above)
         v4i acc[2][8];
         int ctlow[8];
 #pragma unroll
         for (int cb = 0; cb < 8; cb++) {
-            ctlow[cb] = (s_ct[buf][cb * 16 + l16] << 7) | low[cb];
-            acc[0][cb] = v4i{0, 0, 0, 0};
-            acc[1][cb] = acc[0][cb];
+            if constexpr (!GUIDED) {
+                ctlow[cb] = (s_ct[buf][cb * 16 + l16] << 7) | low[cb];
+                acc[0][cb] = v4i{0, 0, 0, 0};
+                acc[1][cb] = acc[0][cb];
+            } else {
+                const int ct = s_ct[buf][cb * 16 + l16];
+                ctlow[cb] = low[cb];
+#pragma unroll
+                for (int rb = 0; rb < 2; rb++) {
+                    const int mb = (int)(rec[rb * 2 + (cb >> 2)] >> ((cb & 3) * 8));
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        acc[rb][cb][i] = ct - ((mb >> i) & 1) * kBiasFail - ((mb >> (4 + i)) & 1) * kBiasNoGood;
+                }
+            }
         }
         const uint8_t* sb = s_b[buf];
 #pragma unroll
@@ -288,6 +463,25 @@ __global__ __launch_bounds__(256) void k_match_pairs(const uint8_t* __restrict__
                 if (row < nA) part[(size_t)it.part_base + row] = Top2{M[rb][i], I[rb][i], S2[rb][i]};
             }
     }
+}
+
+__global__ __launch_bounds__(256) void k_match_pairs(const uint8_t* __restrict__ S,
+                                                     const sgplan::Item* __restrict__ items,
+                                                     Top2* __restrict__ part) {
+    match_pairs_item<false>(S, items, part, nullptr, 0, nullptr, nullptr, nullptr);
+}
+
+// The guided work item: the pair's matrices are geom[Item::pair] (a missing matrix is the
+// identity with its threshold at 1e20, filled in by the host).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_match_pairs_guided(const uint8_t* __restrict__ S,
+                                                            const sgplan::Item* __restrict__ items,
+                                                            Top2* __restrict__ part,
+                                                            const float* __restrict__ loc,
+                                                            int loc_stride,
+                                                            const GuidedParams* __restrict__ geom) {
+    __shared__ uint32_t s_pass[kPanel * kPassPitch];      // [set-1 point][word of set-2 points]
+    __shared__ uint32_t s_good[kPanel / 8 * kPassPitch];  // [8-point block of set 1][word]
+    match_pairs_item<true>(S, items, part, loc, loc_stride, geom, s_pass, s_good);
 }
 
 // One workgroup per (side, panel), a thread per row: merge the side's column chunks (equal maxima
@@ -430,6 +624,15 @@ hipError_t launch_match_pairs(const uint8_t* s8, const sgplan::Item* items, int 
                               hipStream_t stream) {
     if (nitems <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_match_pairs, dim3(nitems), dim3(256), 0, stream, s8, items, part);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_pairs_guided(const uint8_t* s8, const sgplan::Item* items, int nitems,
+                                     Top2* part, const float* loc, int loc_stride,
+                                     const GuidedParams* geom, hipStream_t stream) {
+    if (nitems <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_match_pairs_guided, dim3(nitems), dim3(256), 0, stream, s8, items, part,
+                       loc, loc_stride, geom);
     return hipGetLastError();
 }
 

@@ -37,6 +37,7 @@ C_API = [
     "sgpu_quantize_descriptors_gpu", "sgpu_feature_descriptors_u8", "sgpu_copy_features_u8",
     "sgpu_match_batch", "sgpu_match_images", "sgpu_debug_match_plan_stats",
     "sgpu_debug_set_duo_strips", "sgpu_debug_pyramid_plan",
+    "sgpu_match_batch_guided", "sgpu_match_images_guided",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -116,6 +117,12 @@ def lib():
                                        c.c_int, c.c_int, vp, c.c_int64, vp, c.c_int]
         L.sgpu_match_images.argtypes = [vp, vp, c.c_int, c.c_float, c.c_float, c.c_int, c.c_int,
                                         vp, c.c_int64, vp]
+        L.sgpu_match_batch_guided.argtypes = [vp, vp, vp, vp, c.c_int, vp, c.c_int, vp, vp,
+                                              c.c_float, c.c_float, c.c_float, c.c_float,
+                                              c.c_int, c.c_int, vp, c.c_int64, vp, c.c_int]
+        L.sgpu_match_images_guided.argtypes = [vp, vp, c.c_int, vp, vp, c.c_float, c.c_float,
+                                               c.c_float, c.c_float, c.c_int, c.c_int, vp,
+                                               c.c_int64, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -538,6 +545,63 @@ class SiftContext:
             return lib().sgpu_match_images(self._ctx, pr.ctypes.data if npairs else None, npairs,
                                            distmax, ratiomax, mbm, mm, out.ctypes.data, cp,
                                            counts.ctypes.data)
+        return self._pair_results(call, pairs, sizes, max_match, cap)
+
+    @staticmethod
+    def _pair_matrices(M, npairs, name):
+        """H / F of a guided pair list: [npairs][3][3] (or [npairs][9]) float32, or None."""
+        if M is None:
+            return None
+        m = np.ascontiguousarray(M, np.float32)
+        if m.size != 9 * npairs or m.ndim < 2 or m.shape[0] != npairs:
+            raise ValueError(f"{name} must be [npairs][3][3] ({npairs} pairs), got {m.shape}")
+        return m.reshape(npairs, 9)
+
+    def match_batch_guided(self, desc_u8: np.ndarray, loc: np.ndarray, offsets, pairs, H=None,
+                           F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0, mbm=1,
+                           max_match=None, cap=None):
+        """Guided matching of many set pairs in one call (sgpu_match_batch_guided): the sets of
+        match_batch with their locations loc [rows][2] (x, y), and per pair p its own H[p] / F[p]
+        ([npairs][3][3], or None for all pairs).  Returns one [m, 2] int32 array per pair, each
+        what match_guided(set a, set b, loc a, loc b, H[p], F[p]) returns."""
+        d = np.ascontiguousarray(desc_u8, np.uint8).reshape(-1, 128)
+        lc = np.ascontiguousarray(loc, np.float32)
+        if lc.ndim != 2 or lc.shape != (len(d), 2):
+            raise ValueError(f"locations must be [rows][2] for {len(d)} rows, got {lc.shape}")
+        off = np.ascontiguousarray(offsets, np.int64)
+        nsets = len(off) - 1
+        if nsets < 0 or (nsets >= 0 and len(off) and off[-1] > len(d)):
+            raise ValueError("offsets do not fit the descriptor buffer")
+        sizes = np.diff(off)
+        npr = len(np.asarray(pairs, np.int32).reshape(-1, 2))
+        hm = self._pair_matrices(H, npr, "H")
+        fm = self._pair_matrices(F, npr, "F")
+
+        def call(pr, npairs, mm, out, cp, counts):
+            return lib().sgpu_match_batch_guided(
+                self._ctx, d.ctypes.data if len(d) else None, lc.ctypes.data if len(lc) else None,
+                off.ctypes.data, nsets, pr.ctypes.data if npairs else None, npairs,
+                None if hm is None else hm.ctypes.data, None if fm is None else fm.ctypes.data,
+                distmax, ratiomax, hdistmax, fdistmax, mbm, mm, out.ctypes.data, cp,
+                counts.ctypes.data, SGPU_INPUT_HOST)
+        return self._pair_results(call, pairs, sizes, max_match, cap)
+
+    def match_images_guided(self, pairs, H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0,
+                            fdistmax=16.0, mbm=1, max_match=None, cap=None):
+        """Image pairs of the last extract matched under per-pair geometry on the device
+        (sgpu_match_images_guided): descriptors as match_images, locations = x, y of the batch's
+        device keys; neither leaves HBM.  H / F: [npairs][3][3] or None."""
+        npr = len(np.asarray(pairs, np.int32).reshape(-1, 2))
+        hm = self._pair_matrices(H, npr, "H")
+        fm = self._pair_matrices(F, npr, "F")
+        sizes = np.array([self.count(i) for i in range(self.batch)], np.int64)
+
+        def call(pr, npairs, mm, out, cp, counts):
+            return lib().sgpu_match_images_guided(
+                self._ctx, pr.ctypes.data if npairs else None, npairs,
+                None if hm is None else hm.ctypes.data, None if fm is None else fm.ctypes.data,
+                distmax, ratiomax, hdistmax, fdistmax, mbm, mm, out.ctypes.data, cp,
+                counts.ctypes.data)
         return self._pair_results(call, pairs, sizes, max_match, cap)
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
