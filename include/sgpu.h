@@ -398,6 +398,17 @@ int sgpu_comm_allreduce_f64(sgpu_ctx* ctx, double* v, int n, int op_max);
                                               SGPU_DEBUG_GAUSS_TILE_ALWAYS tiles every one) */
 
 int sgpu_debug_set_flags(sgpu_ctx* ctx, int flags);
+/* How a batch's orientation and descriptor kernels get their work, a test / A-B
+ * hook -- the same bits in every form.  (A setter of its own: every flag bit below the band
+ * height field is taken.)  QUEUE (shipped): resident one-wave workgroups fed from the extract's
+ * work counters (k_orientation_queue, k_descriptor_queue); STATIC_ORIENTATION, STATIC_DESCRIPTOR:
+ * that kernel through a grid that covers the work (k_orientation, k_descriptor_flat); STATIC:
+ * both.  SGPU_FEATURE_QUEUE=on / ori / desc / off at context creation sets the same. */
+#define SGPU_FEATURES_QUEUE 0
+#define SGPU_FEATURES_STATIC_ORIENTATION 1
+#define SGPU_FEATURES_STATIC_DESCRIPTOR 2
+#define SGPU_FEATURES_STATIC 3
+int sgpu_debug_set_feature_queue(sgpu_ctx* ctx, int mode);
 /* The batch pyramid's launch plan, a test / A-B hook -- the levels are the same
  * bits in every plan.  trio: three-level launches (k_gauss_trio): none (shipped), on levels of
  * >= 512 MB, or wherever the widths and the decimation allow (SGPU_TRIO=off / on / always at

@@ -151,12 +151,21 @@ struct sgpu_ctx {
     size_t wide_desc_max = SGK_WIDE_DESC_MAX;   // feature counts (of the previous call) up to which
                                            // descriptors run a workgroup per feature
                                            // (SGPU_WIDE_DESC_MAX)
+    size_t wave_orient_max = kWaveOrientationMax;   // candidate counts (of the previous call) up to
+                                           // which orientation runs a wave per candidate
+                                           // (SGPU_WAVE_ORIENT_MAX; a test hook: 0 keeps the quad
+                                           // forms for small batches)
     bool unit_input = true;                // the last extract's input lies in [0, 1] (not a caller's f32)
     bool tile_duo = false;                 // tile duos when every level is tiled (SGPU_TILE_DUO=on;
                                            // measured slower)
     int tile_mb = SGK_TILE_MB;             // levels of at most this many MB: 2-D tile launches
                                            // (SGPU_GAUSS_TILE_MB; k_gauss_tile)
     int env_flags = 0;                     // debug flags set from the environment at creation
+    // the feature stages' persistent form: the resident grids of this device,
+    // and which of the two kernels take it (sgpu_debug_set_feature_queue; SGPU_FEATURE_QUEUE=off
+    // / ori / desc / on at creation, an A/B hook)
+    sgk::FeatureQueue fq{};
+    bool queue_ori = true, queue_desc = true;
     // sgpu_set_host_output: page-locked host buffers the next one-image extract fills in its own
     // stream (armed until that extract); done = the last extract filled them
     struct HostOut {
@@ -423,6 +432,7 @@ int sgpu_ctx_create(int device, const sgpu_options* opt, sgpu_ctx** out) {
                   part_streams(p[0], PS_LO) == SGPU_OK && part_streams(p[1], PS_OCT) == SGPU_OK &&
                   part_streams(p[2], PS_MAIN) == SGPU_OK && part_streams(p[2], PS_LO) == SGPU_OK &&
                   part_streams(p[1], PS_MAIN) == SGPU_OK && part_streams(p[1], PS_LO) == SGPU_OK;
+        ok = ok && sgk::feature_queue_grids(&ctx->fq) == hipSuccess;
         for (int i = 0; ok && i < 2; i++)
             ok = hipEventCreateWithFlags(&ctx->up_ev[i], hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&ctx->down_ev[i], hipEventDisableTiming) == hipSuccess;
@@ -477,9 +487,25 @@ int sgpu_ctx_create(int device, const sgpu_options* opt, sgpu_ctx** out) {
     }
     if (const char* ev = getenv("SGPU_WIDE_DESC_MAX"))
         if (atoll(ev) >= 0) ctx->wide_desc_max = (size_t)atoll(ev);
+    if (const char* ev = getenv("SGPU_WAVE_ORIENT_MAX"))
+        if (atoll(ev) >= 0) ctx->wave_orient_max = (size_t)atoll(ev);
     if (const char* ev = getenv("SGPU_EXTREMA")) {   // A/B hook of the tile extremum kernel
         if (!strcmp(ev, "wave")) ctx->debug_flags |= SGPU_DEBUG_EXTREMA_TILE_OFF;
     }
+    if (const char* ev = getenv("SGPU_FEATURE_QUEUE")) {   // A/B hook of the persistent feature kernels
+        // (any other value leaves the shipped forms)
+        if (!strcmp(ev, "on") || !strcmp(ev, "ori") || !strcmp(ev, "desc") || !strcmp(ev, "off")) {
+            ctx->queue_ori = !strcmp(ev, "on") || !strcmp(ev, "ori");
+            ctx->queue_desc = !strcmp(ev, "on") || !strcmp(ev, "desc");
+        }
+    }
+    // test hook: at most this many resident workgroups per feature kernel, so that small batches
+    // take most of their units from the work counters (the launchers keep one wave per counter)
+    if (const char* ev = getenv("SGPU_FEATURE_QUEUE_GRID"))
+        if (atoi(ev) >= 1) {
+            ctx->fq.ori_grid = std::min(ctx->fq.ori_grid, atoi(ev));
+            ctx->fq.desc_grid = std::min(ctx->fq.desc_grid, atoi(ev));
+        }
     if (const char* ev = getenv("SGPU_TILE_DUO"))
         ctx->tile_duo = !strcmp(ev, "on");
     if (const char* ev = getenv("SGPU_MATCH_PRUNE"))   // A/B hook of the pruned column side
@@ -604,7 +630,9 @@ static int layout_part(sgpu_ctx* ctx, Part& pt) {
     ALLOCCHK(ctx, pt.img_off_dev.ensure((size_t)(n + 2) * sizeof(int64_t)));
     ALLOCCHK(ctx, pt.cand.ensure(nc * sizeof(float4)));
     ALLOCCHK(ctx, pt.info.ensure(nc * sizeof(int2)));
-    ALLOCCHK(ctx, pt.ocount.ensure(nc * sizeof(uint32_t)));
+    // (+ the feature queue's work counters after the counts, from the next 128-byte line on,
+    // zeroed with them)
+    ALLOCCHK(ctx, pt.ocount.ensure((sgk::feature_queue_base(nc) + sgk::kFeatureQueueWords) * sizeof(uint32_t)));
     ALLOCCHK(ctx, pt.eoff.ensure((nc + 1) * sizeof(uint32_t)));
     ALLOCCHK(ctx, pt.feat.ensure(ne_cap * sizeof(float4)));
     ALLOCCHK(ctx, pt.feat_info.ensure(ne_cap * sizeof(int2)));
@@ -702,7 +730,7 @@ static int build_level_ops(sgpu_ctx* ctx, Part& pt, const uint8_t* src8, const f
                 op.zero.p[1] = pt.mask.as<uint32_t>();
                 op.zero.n[1] = (size_t)pt.mask_words;
                 op.zero.p[2] = pt.ocount.as<uint32_t>();
-                op.zero.n[2] = pt.cand_cap;
+                op.zero.n[2] = sgk::feature_queue_base(pt.cand_cap) + sgk::kFeatureQueueWords;   // + the work counters
             }
             pt.levels.push_back(sgpyr::LevelDesc{o, k, op.fw, op.w, op.h, op.batch, dk,
                                                  op.src_u8 != nullptr,
@@ -857,12 +885,18 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
     if (wait_lo) HIPCHK(ctx, hipStreamWaitEvent(st, wait_lo, 0));   // previous features read out
     const uint32_t* n_cand_dev = pt.row_base.as<uint32_t>() + pt.total_rows;
     if (!pt.one_stream)
-        HIPCHK(ctx, sgk::launch_zero(pt.ocount.as<uint32_t>(), nc, nullptr, 0, nullptr, 0, st));
+        HIPCHK(ctx, sgk::launch_zero(pt.ocount.as<uint32_t>(), sgk::feature_queue_base(nc) + sgk::kFeatureQueueWords,
+                                     nullptr, 0, nullptr, 0, st));
+    // the persistent form of the quad orientation and the one-wave descriptor kernels: this
+    // part's own work counters, behind its orientation counts and zeroed with them (the parts of
+    // a batch and the batches of sgpu_extract_stream run side by side)
+    sgk::FeatureQueue fq = ctx->fq;
+    fq.next = pt.ocount.as<uint32_t>() + sgk::feature_queue_base(nc);
     const int cand_grid = (int)std::min(nc, pt.cand_hint ? pt.cand_hint : nc);
     // few candidates (a single image): one wave per candidate instead of a quad, so that the
     // SIMDs are filled and each window is walked 64 samples at a time (same bits)
     const bool ori_wave = (ctx->debug_flags & SGPU_DEBUG_ORIENT_WAVE) ||
-                          (pt.cand_hint > 0 && pt.cand_hint <= kWaveOrientationMax);
+                          (pt.cand_hint > 0 && pt.cand_hint <= ctx->wave_orient_max);
     const int feat_grid = (int)std::min(ne_cap, pt.feat_hint ? pt.feat_hint : ne_cap);
     // few features (a single image): a workgroup of 4 waves per feature instead of one wave
     // (k_descriptor_wide, same bits)
@@ -872,7 +906,8 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
     HIPCHK(ctx, sgk::launch_orientation(pyr, pt.mask.as<uint32_t>(), pt.row_base.as<uint32_t>(),
                                         pt.total_rows, n_cand_dev, (int)nc, cand_grid, fp,
                                         pt.cand.as<float4>(), pt.info.as<int2>(),
-                                        pt.ocount.as<uint32_t>(), st, ori_wave));
+                                        pt.ocount.as<uint32_t>(), st, ori_wave,
+                                        ctx->queue_ori ? &fq : nullptr));
     if (O.feature_count_threshold > 0 && fp.num_orientation >= 2)   // LimitFeatureCount(1)
         HIPCHK(ctx, sgk::launch_limit_oriented(pt.ocount.as<uint32_t>(), pt.row_base.as<uint32_t>(),
                                                fp, O.feature_count_threshold, O.truncate_method,
@@ -917,7 +952,8 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
         HIPCHK(ctx, sgk::launch_descriptor(pyr, pt.feat.as<float4>(), pt.feat_info.as<int2>(),
                                            n_feat_dev, feat_grid, fp, pt.desc.as<float>(), st,
                                            nullptr, false, exact_desc, dual_desc, desc_wide,
-                                           host_in_desc ? &hcopy : nullptr));
+                                           host_in_desc ? &hcopy : nullptr,
+                                           ctx->queue_desc ? &fq : nullptr));
     HIPCHK(ctx, rec(5, st));
     if (pt.copied_out && !host_in_desc)
         HIPCHK(ctx, sgk::launch_copy_out(pt.keys.as<float4>(), O.descriptors ? pt.desc.as<float>() : nullptr,
@@ -2433,6 +2469,13 @@ static_assert(SGPU_DUO_STRIPS_RULE == sgk::kDuoStripsRule && SGPU_DUO_STRIPS_WAV
 int sgpu_debug_set_duo_strips(sgpu_ctx* ctx, int mode) {
     if (!ctx || mode < SGPU_DUO_STRIPS_RULE || mode > SGPU_DUO_STRIPS_COOP) return SGPU_EINVAL;
     ctx->duo_strips = mode;
+    return SGPU_OK;
+}
+
+int sgpu_debug_set_feature_queue(sgpu_ctx* ctx, int mode) {
+    if (!ctx || mode < SGPU_FEATURES_QUEUE || mode > SGPU_FEATURES_STATIC) return SGPU_EINVAL;
+    ctx->queue_ori = !(mode & SGPU_FEATURES_STATIC_ORIENTATION);
+    ctx->queue_desc = !(mode & SGPU_FEATURES_STATIC_DESCRIPTOR);
     return SGPU_OK;
 }
 

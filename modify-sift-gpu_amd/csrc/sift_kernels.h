@@ -166,16 +166,43 @@ hipError_t launch_zero(uint32_t* a, size_t na, uint32_t* b, size_t nb, uint32_t*
 hipError_t launch_scan(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp,
                        hipStream_t stream);
 
+// The work queue of an extract's two feature stages in their persistent form:
+// resident workgroups that take their work from counters instead of a grid that covers it.
+// next: the extract's own kFeatureQueueWords words -- kQueueCounters counters of the
+// orientation's groups of 16 candidates, then as many of the descriptor's features, each on a
+// 128-byte line of its own -- all zero when the orientation kernel starts (the caller zeroes
+// them with the extract's other counters).  The grids are what the device holds at once
+// (feature_queue_grids; a larger one only adds workgroups that exit at once).
+constexpr int kQueueCounters = 8;    // counters per stage (1 saturates at 2 x 10^5 features a
+                                     // step; 2 to 16 measured alike)
+constexpr int kQueueStride = 32;     // words between them
+constexpr size_t kFeatureQueueWords = 2 * kQueueCounters * kQueueStride;
+// where the counters start behind n_cand_cap orientation counts in one (256-byte aligned)
+// allocation: the next multiple of kQueueStride words, so that no counter shares a line
+constexpr size_t feature_queue_base(size_t n_cand_cap) {
+    return (n_cand_cap + kQueueStride - 1) / kQueueStride * kQueueStride;
+}
+struct FeatureQueue {
+    uint32_t* next = nullptr;
+    int ori_grid = 0;     // one-wave workgroups of the orientation kernel
+    int desc_grid = 0;    // workgroups of desc_waves (1 or 2) waves of the descriptor kernel
+    int desc_waves = 1;
+};
+// The resident grids of the current device, from the kernels' occupancy (once per context).
+hipError_t feature_queue_grids(FeatureQueue* q);
+
 // Keypoint materialisation + orientation: a quad per detected keypoint (wave_per_candidate: a
 // wave, for few candidates), grid-stride over min(*n_cand_dev, n_cand_cap) keypoints (the grid
-// is sized from grid_hint).  Both forms give the same bits.
+// is sized from grid_hint).  queue (quad form only): the persistent form.  All forms give the
+// same bits.
 // out4: (x, y, s, packed orientations) in octave coordinates; info: (image, level id);
 // ocount: number of oriented features the keypoint expands to.
 hipError_t launch_orientation(const float* pyr, const uint32_t* mask, const uint32_t* row_base,
                               int total_rows, const uint32_t* n_cand_dev, int n_cand_cap,
                               int grid_hint, const FeatureParams& fp, float4* out4, int2* info,
                               uint32_t* ocount, hipStream_t stream,
-                              bool wave_per_candidate = false);
+                              bool wave_per_candidate = false,
+                              const FeatureQueue* queue = nullptr);
 
 // Expansion into oriented features (+ image-coordinate keypoints).  io (optional): the same
 // launch also writes the extract's readback record (io.off[0] = candidate count, io.off[1 + b]
@@ -207,6 +234,7 @@ hipError_t launch_copy_out(const float4* keys, const float* desc, const uint32_t
 // features; the grid is then one workgroup per feature up to n_feat_cap) -- the same bits.
 // host (wide only): keys[e], descriptor row e (e < cap) and the rec_n (<= 256) int64 words of rec
 // also to page-locked host memory, in place of a launch_copy_out after the kernel.
+// queue: k_descriptor_flat in its persistent form (ignored by the other kernels) -- the same bits.
 struct HostCopy {
     const float4* keys = nullptr;
     const int64_t* rec = nullptr;
@@ -220,7 +248,8 @@ hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* f
                              const uint32_t* n_feat_dev, int n_feat_cap, const FeatureParams& fp,
                              float* desc, hipStream_t stream, const int* out_index = nullptr,
                              bool rect = false, bool exact = false, bool dual = false,
-                             bool wide = false, const HostCopy* host = nullptr);
+                             bool wide = false, const HostCopy* host = nullptr,
+                             const FeatureQueue* queue = nullptr);
 
 // Caller-supplied keypoints: strongest orientation into feat[e].w (num_orientation != 0, else
 // 0) and the image-coordinate key at keys_out[index[e]].

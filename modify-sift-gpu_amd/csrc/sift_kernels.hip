@@ -1702,6 +1702,59 @@ __global__ __launch_bounds__(256) void k_orientation(const float* __restrict__ p
         orientation_one(f, sub, vote_l, pyr, mask, row_base, total_rows, fp, out4, info, ocount);
 }
 
+// A wave's walk over the units of a feature stage.  The wave's first unit is its
+// own index in the grid, without a counter access (a whole grid asking a counter at the launch is
+// served one wave after the other: 60-90 us for a resident grid); every further one comes from a
+// work counter.  kQueueCounters counters, kQueueStride words apart, share the units past the
+// grid's first ones: counter k hands out units nwaves + k, nwaves + k + kQueueCounters, ... to
+// the waves whose index is k mod kQueueCounters (same-address atomics are served one at a time
+// by the memory side, ~11.5 ns each: one counter for 2 x 10^5 features takes longer than the
+// features; interleaved, the counters hold equal shares of the work, so no wave needs another's
+// counter).  In two steps, so that a kernel can ask for its next unit before the end of the
+// current one and have the counter's round trip run beside the rest of it: queue_ask returns
+// lane 0's ticket, queue_unit turns it into the wave's next unit.
+// (Relaxed: the counters order nothing, every unit is computed from buffers that earlier
+// launches finished.)
+__device__ __forceinline__ uint32_t queue_ask(uint32_t* next, uint32_t wave) {
+    uint32_t i = 0;
+    if ((threadIdx.x & 63) == 0)
+        i = __hip_atomic_fetch_add(next + (wave % kQueueCounters) * kQueueStride, 1u,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return i;
+}
+__device__ __forceinline__ uint32_t queue_unit(uint32_t ticket, uint32_t wave, uint32_t nwaves) {
+    return nwaves + __builtin_amdgcn_readfirstlane(ticket) * kQueueCounters + wave % kQueueCounters;
+}
+
+// k_orientation as resident one-wave workgroups fed from work counters: the
+// grid is the number of waves the device holds at once, and each wave takes groups of 16
+// candidates (a quad each, as above) until the candidates are used up, so a wave slot is
+// refilled as soon as its own 16 candidates are done.  Candidate f is computed by the same code
+// and written to the same slot as above.  The counters are zero at the launch; a surplus
+// workgroup finds nothing to do and exits (no workgroup waits for another).
+__global__ __launch_bounds__(64) void k_orientation_queue(const float* __restrict__ pyr,
+                                                          const uint32_t* __restrict__ mask,
+                                                          const uint32_t* __restrict__ row_base,
+                                                          int total_rows,
+                                                          const uint32_t* __restrict__ n_cand_dev,
+                                                          uint32_t cap, const FeatureParams fp,
+                                                          float4* __restrict__ out4,
+                                                          int2* __restrict__ info,
+                                                          uint32_t* __restrict__ ocount,
+                                                          uint32_t* __restrict__ next) {
+    __shared__ float s_vote[16 * 37];
+    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    const uint32_t n = min(*n_cand_dev, cap);
+    const uint32_t groups = (n + 15) / 16;
+    float* vote_l = s_vote + slot * 37;
+    for (uint32_t g = blockIdx.x; g < groups;
+         g = queue_unit(queue_ask(next, blockIdx.x), blockIdx.x, gridDim.x)) {
+        const uint32_t f = 16 * g + slot;   // uniform per quad
+        if (f < n)
+            orientation_one(f, sub, vote_l, pyr, mask, row_base, total_rows, fp, out4, info, ocount);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // -fo != 0: the first octave's input.  src value of input pixel k of the flat tw x h buffer
 // the reference binds (_inputTex, PyramidCU.cpp:949-958): u8 -> p / 255.0f as the host
@@ -3034,6 +3087,37 @@ __global__ __launch_bounds__(256) SGK_FLAT_ATTR void k_descriptor_flat(const flo
                         out_index ? (uint32_t)out_index[e] : e, s_flat[wave]);
 }
 
+// k_descriptor_flat as resident workgroups of NW waves (1; 2 where a compute unit holds more
+// waves that way) fed from work counters: the grid is what the device holds at
+// once, and each wave takes one feature at a time until *n_feat_dev are done, into a histogram
+// of its own, so its slot is refilled as soon as its own feature is finished.  Feature e is
+// computed by the same code and written to the same row as above.  The counters are zero at the
+// launch; surplus waves find nothing to do and exit (no wave waits for another).
+template <int NW>
+__global__ __launch_bounds__(64 * NW) SGK_FLAT_ATTR void k_descriptor_queue(
+    const float* __restrict__ pyr, const float4* __restrict__ feat,
+    const int2* __restrict__ feat_info, const uint32_t* __restrict__ n_feat_dev,
+    const FeatureParams fp, float* __restrict__ desc, const int* __restrict__ out_index,
+    uint32_t* __restrict__ next) {
+    __shared__ __attribute__((aligned(16))) float s_flat[NW][kFlatWords];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = NW == 1 ? 0u : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float* sh = s_flat[wave];
+    const uint32_t n = *n_feat_dev;
+    const uint32_t wv = blockIdx.x * NW + wave, nwaves = gridDim.x * NW;
+    for (uint32_t e = wv; e < n;) {   // descriptor_flat(e), and:
+        flat_accumulate(e, lane, pyr, feat, feat_info, fp, sh, 0, 1);
+        const uint32_t out = out_index ? (uint32_t)out_index[e] : e;
+        const bool narrow = flat_narrow(fp, flat_half_box(feat[e], fp));
+        // the next feature asked for once this one's window is read: the counter's round trip
+        // (memory-side, microseconds) runs beside the histogram's summing and normalisation,
+        // which load nothing
+        const uint32_t ticket = queue_ask(next, wv);
+        flat_finish(lane, fp, desc, out, sh, 1, narrow);
+        e = queue_unit(ticket, wv, nwaves);
+    }
+}
+
 // A workgroup of NWV (4) waves per feature, for few features (one image: ~1,500 features are ~1.5
 // waves per SIMD under one wave each, and each wave walks its window alone).  The waves take every
 // NWV-th 64-pixel step of the window into histograms of their own; wave 0 sums all of them.  The
@@ -3509,11 +3593,40 @@ hipError_t launch_scan(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tm
     return hipGetLastError();
 }
 
+hipError_t feature_queue_grids(FeatureQueue* q) {
+    int dev = 0, cus = 0, ori = 0, d1 = 0, d2 = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&ori, k_orientation_queue, 64, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&d1, k_descriptor_queue<1>, 64, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&d2, k_descriptor_queue<2>, 128, 0);
+    if (e != hipSuccess) return e;
+    if (cus <= 0 || ori <= 0 || d1 <= 0 || d2 <= 0) return hipErrorInvalidValue;
+    // the descriptor in two-wave workgroups only where a compute unit holds more waves that way
+    // (a limit on its workgroups, or the LDS allocation's granularity)
+    q->desc_waves = 2 * d2 > d1 ? 2 : 1;
+    q->ori_grid = ori * cus;
+    q->desc_grid = (q->desc_waves == 2 ? d2 : d1) * cus;
+    return hipSuccess;
+}
+
 hipError_t launch_orientation(const float* pyr, const uint32_t* mask, const uint32_t* row_base,
                               int total_rows, const uint32_t* n_cand_dev, int n_cand_cap,
                               int grid_hint, const FeatureParams& fp, float4* out4, int2* info,
-                              uint32_t* ocount, hipStream_t stream, bool wave_per_candidate) {
+                              uint32_t* ocount, hipStream_t stream, bool wave_per_candidate,
+                              const FeatureQueue* queue) {
     if (n_cand_cap <= 0) return hipSuccess;
+    if (queue && !wave_per_candidate) {
+        if (!queue->next || queue->ori_grid <= 0) return hipErrorInvalidValue;
+        // no more workgroups than groups of 16 the capacity holds (the rest would only exit), and
+        // at least one wave per counter (a counter's units are taken by its own waves only)
+        const long long groups = ((long long)n_cand_cap + 15) / 16;
+        const unsigned grid = (unsigned)std::max<long long>(kQueueCounters, std::min<long long>(groups, queue->ori_grid));
+        hipLaunchKernelGGL(k_orientation_queue, dim3(grid), dim3(64), 0, stream, pyr, mask,
+                           row_base, total_rows, n_cand_dev, (uint32_t)n_cand_cap, fp, out4, info,
+                           ocount, queue->next);
+        return hipGetLastError();
+    }
     if (wave_per_candidate) {
         const unsigned grid = (unsigned)std::max(1LL, std::min(((long long)grid_hint + 3) / 4, 8192LL));
         hipLaunchKernelGGL(k_orientation_wave, dim3(grid), dim3(256), 0, stream, pyr, mask,
@@ -3586,7 +3699,8 @@ hipError_t launch_orient_keys(const float* pyr, float4* feat, const int2* feat_i
 hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* feat_info,
                              const uint32_t* n_feat_dev, int n_feat_cap, const FeatureParams& fp,
                              float* desc, hipStream_t stream, const int* out_index,
-                             bool rect, bool exact, bool dual, bool wide, const HostCopy* host) {
+                             bool rect, bool exact, bool dual, bool wide, const HostCopy* host,
+                             const FeatureQueue* queue) {
     if (n_feat_cap <= 0) return hipSuccess;
     if (host && (!wide || exact || rect || dual || host->rec_n < 0 || host->rec_n > 256 ||
                  !host->hkeys || !host->hrec || !host->keys || !host->rec))
@@ -3617,6 +3731,21 @@ hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* f
         else
             hipLaunchKernelGGL(k_descriptor_wide<4>, dim3(wgrid), dim3(256), 0, stream, pyr, feat,
                                feat_info, n_feat_dev, fp, desc, out_index, hc);
+        return hipGetLastError();
+    }
+    if (!exact && !rect && SGK_DESC_FLAT && !dual && queue) {
+        const int nw = queue->desc_waves;
+        if (!queue->next || queue->desc_grid <= 0 || (nw != 1 && nw != 2)) return hipErrorInvalidValue;
+        // the descriptor's counters follow the orientation's; the grid as in launch_orientation
+        uint32_t* qa = queue->next + kQueueCounters * kQueueStride;
+        const long long wgs = ((long long)n_feat_cap + nw - 1) / nw;
+        const unsigned qgrid = (unsigned)std::max<long long>(kQueueCounters, std::min<long long>(wgs, queue->desc_grid));
+        if (nw == 2)
+            hipLaunchKernelGGL(k_descriptor_queue<2>, dim3(qgrid), dim3(128), 0, stream, pyr, feat,
+                               feat_info, n_feat_dev, fp, desc, out_index, qa);
+        else
+            hipLaunchKernelGGL(k_descriptor_queue<1>, dim3(qgrid), dim3(64), 0, stream, pyr, feat,
+                               feat_info, n_feat_dev, fp, desc, out_index, qa);
         return hipGetLastError();
     }
     if (!exact && !rect && SGK_DESC_FLAT && !dual) {

@@ -36,7 +36,7 @@ C_API = [
     "sgpu_set_host_output", "sgpu_debug_set_schedule", "sgpu_debug_set_match_prune",
     "sgpu_quantize_descriptors_gpu", "sgpu_feature_descriptors_u8", "sgpu_copy_features_u8",
     "sgpu_match_batch", "sgpu_match_images", "sgpu_debug_match_plan_stats",
-    "sgpu_debug_set_duo_strips", "sgpu_debug_pyramid_plan",
+    "sgpu_debug_set_duo_strips", "sgpu_debug_pyramid_plan", "sgpu_debug_set_feature_queue",
     "sgpu_match_batch_guided", "sgpu_match_images_guided",
 ]
 
@@ -91,6 +91,7 @@ def lib():
         L.sgpu_debug_set_schedule.argtypes = [vp, c.c_int, c.c_int]
         L.sgpu_debug_set_match_prune.argtypes = [vp, c.c_int]
         L.sgpu_debug_set_duo_strips.argtypes = [vp, c.c_int]
+        L.sgpu_debug_set_feature_queue.argtypes = [vp, c.c_int]
         L.sgpu_debug_geometry.argtypes = [vp, P(c.c_int), vp, c.c_int]
         L.sgpu_debug_gaussian.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
         L.sgpu_debug_candidates.argtypes = [vp, vp, vp, c.c_int, P(c.c_int)]
@@ -689,6 +690,14 @@ class SiftContext:
         lane-columns and measured faster), STRIPS_WAVE (a 96-column strip per wave everywhere),
         STRIPS_COOP (the shared strip wherever it is compiled, at any width): the same levels."""
         self._check(lib().sgpu_debug_set_duo_strips(self._ctx, mode), "sgpu_debug_set_duo_strips")
+
+    FEATURES_QUEUE, FEATURES_STATIC_ORIENTATION, FEATURES_STATIC_DESCRIPTOR, FEATURES_STATIC = 0, 1, 2, 3
+
+    def set_feature_queue(self, mode: int = 0):
+        """How a batch's orientation and descriptor kernels get their work
+        (sgpu_debug_set_feature_queue): FEATURES_QUEUE (shipped: resident workgroups fed from work
+        counters), FEATURES_STATIC (grids that cover the work) or one kernel of the two; same bits."""
+        self._check(lib().sgpu_debug_set_feature_queue(self._ctx, mode), "sgpu_debug_set_feature_queue")
 
     def set_match_prune(self, on: bool = True):
         """Plain mutual matching's column side over the rows of set 1 that can change a listed
