@@ -110,7 +110,10 @@ long long sgpu_debug_alloc_count(void);
 /* Extract SIFT features from n gray u8 images of w x h pixels, row stride `stride` bytes,
  * image i at images + i*stride*h.  Replaces SiftGPU::RunSIFT(w, h, data, GL_LUMINANCE,
  * GL_UNSIGNED_BYTE) (SiftGPU.h:176, SiftGPU.cpp:233-268 -> SiftPyramid::RunSIFT,
- * SiftPyramid.cpp:58-216), batched.  Results stay valid until the next extract call. */
+ * SiftPyramid.cpp:58-216), batched.  Results stay valid until the next extract call.
+ * What is read (this and every extract entry below, stride in its own unit): a host buffer is
+ * copied as n * h * stride elements, so the last row's padding must exist; of each row only the
+ * first w & ~3 columns are ever used (a device buffer's padding is never read). */
 int sgpu_extract(sgpu_ctx* ctx, const uint8_t* images, int n, int w, int h, int stride,
                  int flags);
 

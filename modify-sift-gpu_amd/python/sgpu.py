@@ -285,72 +285,108 @@ class SiftContext:
         """Device + pinned allocations the library has made so far (sgpu_debug_alloc_count)."""
         return int(lib().sgpu_debug_alloc_count())
 
-    def stage(self, images: np.ndarray):
-        """Upload a u8 batch [n, h, w] once; extract_staged() then starts from HBM."""
-        a = np.ascontiguousarray(images, np.uint8)
-        if a.ndim == 2:
-            a = a[None]
-        n, h, w = a.shape
-        self._check(lib().sgpu_stage_input(self._ctx, a.ctypes.data, n, w, h, w), "stage")
-        self._staged = (n, h, w)
+    @staticmethod
+    def _padded(images, stride, shape, dtype, channels=1):
+        """A flat buffer of n images whose rows are `stride` elements apart (stride given), or a
+        dense [n, h, w(, c)] array (stride None): (array, n, h, w, stride).  The library reads
+        n * h * stride elements, so the flat buffer must hold them (the last row's padding too)."""
+        if stride is None:
+            a = np.ascontiguousarray(images, dtype)
+            if a.ndim == (2 if channels == 1 else 3):
+                a = a[None]
+            if a.ndim != (3 if channels == 1 else 4):
+                raise ValueError(f"images must be [n, h, w{'' if channels == 1 else ', c'}], got {a.shape}")
+            n, h, w = a.shape[:3]
+            if channels != 1 and a.shape[3] != channels:
+                raise ValueError("channel count does not match the format")
+            return a, n, h, w, w * channels
+        if shape is None:
+            raise ValueError("a row stride needs shape=(n, h, w)")
+        n, h, w = (int(v) for v in shape)
+        a = np.ascontiguousarray(images, dtype).reshape(-1)
+        stride = int(stride)
+        if stride < w * channels or a.size < n * h * stride:
+            raise ValueError(f"{a.size} elements do not hold {n} x {h} rows {stride} apart "
+                             f"of {w * channels}")
+        return a, n, h, w, stride
+
+    def stage(self, images: np.ndarray, stride=None, shape=None):
+        """Upload a u8 batch [n, h, w] once; extract_staged() then starts from HBM.  With
+        stride (bytes between rows): images is the flat buffer and shape = (n, h, w)."""
+        a, n, h, w, stride = self._padded(images, stride, shape, np.uint8)
+        self._check(lib().sgpu_stage_input(self._ctx, a.ctypes.data, n, w, h, stride), "stage")
+        self._staged = (n, h, w, stride)
         return self
 
     def extract_staged(self):
-        n, h, w = self._staged
-        self._check(lib().sgpu_extract(self._ctx, None, n, w, h, w, SGPU_INPUT_STAGED),
+        n, h, w, stride = self._staged
+        self._check(lib().sgpu_extract(self._ctx, None, n, w, h, stride, SGPU_INPUT_STAGED),
                     "sgpu_extract(staged)")
         self.batch = n
         return self
 
-    def extract(self, images: np.ndarray | int, shape=None, device_ptr=False):
-        """images: u8 [n, h, w] (or [h, w]) host array, or an int device pointer with
-        shape=(n, h, w, stride)."""
+    def extract(self, images: np.ndarray | int, shape=None, device_ptr=False, stride=None,
+                dtype=None):
+        """images: u8 or f32 [n, h, w] (or [h, w]) host array; or, with stride (elements between
+        rows), the flat host buffer of shape=(n, h, w); or an int device pointer with
+        shape=(n, h, w, stride) and dtype np.uint8 (default) / np.float32."""
         if device_ptr:
             n, h, w, stride = shape
-            rc = lib().sgpu_extract(self._ctx, ctypes.c_void_p(images), n, w, h, stride,
-                                    SGPU_INPUT_DEVICE)
+            dt = np.dtype(np.uint8 if dtype is None else dtype)
         else:
-            a = np.ascontiguousarray(images)
-            if a.ndim == 2:
-                a = a[None]
-            n, h, w = a.shape
-            if a.dtype == np.uint8:
-                rc = lib().sgpu_extract(self._ctx, a.ctypes.data, n, w, h, w, SGPU_INPUT_HOST)
-            elif a.dtype == np.float32:
-                rc = lib().sgpu_extract_f32(self._ctx, a.ctypes.data, n, w, h, w, SGPU_INPUT_HOST)
-            else:
-                raise TypeError(a.dtype)
+            dt = np.dtype(np.asarray(images).dtype if dtype is None else dtype)
+        if dt not in (np.dtype(np.uint8), np.dtype(np.float32)):
+            raise TypeError(dt)
+        fn = lib().sgpu_extract if dt == np.uint8 else lib().sgpu_extract_f32
+        if device_ptr:
+            rc = fn(self._ctx, ctypes.c_void_p(images), n, w, h, stride, SGPU_INPUT_DEVICE)
+        else:
+            a, n, h, w, stride = self._padded(images, stride, shape, dt)
+            rc = fn(self._ctx, a.ctypes.data, n, w, h, stride, SGPU_INPUT_HOST)
         self._check(rc, "sgpu_extract")
         self.batch = n
         return self
 
     COLOR_FORMATS = {"rgb": 1, "bgr": 2, "rgba": 3, "bgra": 4}
 
-    def extract_color(self, images: np.ndarray, fmt: str = "rgb"):
+    def extract_color(self, images: np.ndarray | int, fmt: str = "rgb", stride=None, shape=None,
+                      device_ptr=False):
         """u8 color images [n, h, w, 3|4] (or [h, w, c]): luminance on the device with the
-        reference's formula (GLTexImage.cpp:834-858), then the usual pipeline."""
-        a = np.ascontiguousarray(images, np.uint8)
-        if a.ndim == 3:
-            a = a[None]
-        n, h, w, c = a.shape
-        if c != (3 if fmt in ("rgb", "bgr") else 4):
-            raise ValueError("channel count does not match the format")
-        self._check(lib().sgpu_extract_color(self._ctx, a.ctypes.data, n, w, h, w * c,
-                                             self.COLOR_FORMATS[fmt], SGPU_INPUT_HOST),
-                    "extract_color")
+        reference's formula (GLTexImage.cpp:834-858), then the usual pipeline.  With stride (bytes
+        between rows): images is the flat buffer of shape=(n, h, w); with device_ptr an int device
+        pointer with shape=(n, h, w, stride)."""
+        c = 3 if fmt in ("rgb", "bgr") else 4
+        if device_ptr:
+            n, h, w, stride = shape
+            rc = lib().sgpu_extract_color(self._ctx, ctypes.c_void_p(images), n, w, h, stride,
+                                          self.COLOR_FORMATS[fmt], SGPU_INPUT_DEVICE)
+        else:
+            a, n, h, w, stride = self._padded(images, stride, shape, np.uint8, c)
+            rc = lib().sgpu_extract_color(self._ctx, a.ctypes.data, n, w, h, stride,
+                                          self.COLOR_FORMATS[fmt], SGPU_INPUT_HOST)
+        self._check(rc, "extract_color")
         self.batch = n
 
-    def extract_stream(self, batches, keys=None, desc=None, cap=None):
+    def extract_stream(self, batches, keys=None, desc=None, cap=None, stride=None, shape=None):
         """Host-in / host-out extraction of a list of u8 batches [n, h, w] (sgpu_extract_stream:
         uploads and downloads overlap the kernels).  keys / desc: optional preallocated [cap, 4] /
-        [cap, 128] float32 outputs (PinnedArray(...).array for overlapped copies).  Returns
+        [cap, 128] float32 outputs (PinnedArray(...).array for overlapped copies).  With stride
+        (bytes between rows): every batch is a flat buffer of shape=(n, h, w).  Returns
         (keys, desc, counts[total images]) trimmed to the features written."""
-        bl = [np.ascontiguousarray(b) for b in batches]
-        if not bl:
+        if not len(batches):
             raise ValueError("no batches")
-        n, h, w = bl[0].shape
-        if any(b.shape != (n, h, w) or b.dtype != np.uint8 for b in bl):
-            raise ValueError("batches must be u8 arrays of one shape")
+        if stride is None:
+            bl = [np.ascontiguousarray(b) for b in batches]
+            n, h, w = bl[0].shape
+            if any(b.shape != (n, h, w) or b.dtype != np.uint8 for b in bl):
+                raise ValueError("batches must be u8 arrays of one shape")
+            stride = w
+        else:
+            if any(np.asarray(b).dtype != np.uint8 for b in batches):
+                raise ValueError("batches must be u8 buffers")
+            bl = [self._padded(b, stride, shape, np.uint8)[0] for b in batches]
+            n, h, w = (int(v) for v in shape)
+            stride = int(stride)
         want_desc = bool(self.opts.descriptors)
 
         def check_out(a, width, name):
@@ -376,7 +412,7 @@ class SiftContext:
             desc = np.zeros((cap, 128), np.float32)
         ptrs = (ctypes.c_void_p * len(bl))(*[b.ctypes.data for b in bl])
         counts = np.zeros(n * len(bl), np.int32)
-        rc = lib().sgpu_extract_stream(self._ctx, ptrs, len(bl), n, w, h, w, keys.ctypes.data,
+        rc = lib().sgpu_extract_stream(self._ctx, ptrs, len(bl), n, w, h, stride, keys.ctypes.data,
                                        desc.ctypes.data if desc is not None else None, cap,
                                        counts.ctypes.data)
         self._check(rc, "sgpu_extract_stream")
@@ -478,8 +514,16 @@ class SiftContext:
             self._check(m, "sgpu_match")
         return out[:m]
 
-    def quantize_gpu(self, desc: np.ndarray) -> np.ndarray:
-        """Float descriptors [n, 128] -> u8 on the device, byte for byte sgpu.quantize()."""
+    def quantize_gpu(self, desc: np.ndarray, device_ptrs=None):
+        """Float descriptors [n, 128] -> u8 on the device, byte for byte sgpu.quantize().
+        device_ptrs = (float descriptors, n, u8 output): int device pointers, written in place
+        (SGPU_INPUT_DEVICE); returns None."""
+        if device_ptrs is not None:
+            src, n, dst = device_ptrs
+            self._check(lib().sgpu_quantize_descriptors_gpu(
+                self._ctx, ctypes.c_void_p(src), n, ctypes.c_void_p(dst), SGPU_INPUT_DEVICE),
+                "sgpu_quantize_descriptors_gpu")
+            return None
         d = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
         out = np.empty(d.shape, np.uint8)
         self._check(lib().sgpu_quantize_descriptors_gpu(self._ctx, d.ctypes.data, d.shape[0],
@@ -607,25 +651,32 @@ class SiftContext:
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
-                     mbm=1, max_match=None):
+                     mbm=1, max_match=None, device_ptrs=None):
         """SiftMatchGPU::GetGuidedSiftMatch (SiftMatch.cpp:663-677): loc1/loc2 [n][2] (x, y),
-        H/F 3x3 or None (defaults of SiftGPU.h:318-321)."""
-        d1 = np.ascontiguousarray(d1, np.uint8)
-        d2 = np.ascontiguousarray(d2, np.uint8)
-        l1 = np.ascontiguousarray(loc1, np.float32)
-        l2 = np.ascontiguousarray(loc2, np.float32)
-        n1, n2 = d1.shape[0], d2.shape[0]
-        if l1.shape != (n1, 2) or l2.shape != (n2, 2):
-            raise ValueError("locations must be [n][2] per descriptor set")
+        H/F 3x3 or None (defaults of SiftGPU.h:318-321).  device_ptrs = (d1, n1, d2, n2, loc1,
+        loc2): int device pointers in place of the four arrays (SGPU_INPUT_DEVICE)."""
+        if device_ptrs is not None:
+            p1, n1, p2, n2, q1, q2 = device_ptrs
+            flags = SGPU_INPUT_DEVICE
+        else:
+            d1 = np.ascontiguousarray(d1, np.uint8)
+            d2 = np.ascontiguousarray(d2, np.uint8)
+            l1 = np.ascontiguousarray(loc1, np.float32)
+            l2 = np.ascontiguousarray(loc2, np.float32)
+            n1, n2 = d1.shape[0], d2.shape[0]
+            if l1.shape != (n1, 2) or l2.shape != (n2, 2):
+                raise ValueError("locations must be [n][2] per descriptor set")
+            p1, p2, q1, q2 = d1.ctypes.data, d2.ctypes.data, l1.ctypes.data, l2.ctypes.data
+            flags = SGPU_INPUT_HOST
         hm = None if H is None else np.ascontiguousarray(H, np.float32).reshape(9)
         fm = None if F is None else np.ascontiguousarray(F, np.float32).reshape(9)
         max_match = n1 if max_match is None else max_match
         out = np.zeros((max(max_match, 1), 2), np.int32)
         m = lib().sgpu_match_guided(
-            self._ctx, d1.ctypes.data, n1, d2.ctypes.data, n2, l1.ctypes.data, l2.ctypes.data,
+            self._ctx, ctypes.c_void_p(p1), n1, ctypes.c_void_p(p2), n2, ctypes.c_void_p(q1),
+            ctypes.c_void_p(q2),
             None if hm is None else hm.ctypes.data, None if fm is None else fm.ctypes.data,
-            distmax, ratiomax, hdistmax, fdistmax, mbm, max_match, out.ctypes.data,
-            SGPU_INPUT_HOST)
+            distmax, ratiomax, hdistmax, fdistmax, mbm, max_match, out.ctypes.data, flags)
         if m < 0:
             self._check(m, "sgpu_match_guided")
         return out[:m]
