@@ -298,11 +298,63 @@ int sgpu_match_images_guided(sgpu_ctx* ctx, const int* image_pairs, int npairs,
                              int mutual_best_match, int max_match,
                              int* out_pairs, int64_t cap, int* out_counts);
 
+/* Geometry of matched pairs: one homography or fundamental matrix per pair of a pair list, by a
+ * fixed budget of RANSAC hypotheses, on the device, in one call -- the step between
+ * sgpu_match_batch / sgpu_match_images and their guided forms.  No reference counterpart:
+ * SiftMatchGPU::GetGuidedSiftMatch takes H and F from the caller (SiftGPU.h:313-321).
+ *
+ * loc, set_offsets, set_pairs: as sgpu_match_batch_guided (loc host memory, or device memory with
+ * SGPU_INPUT_DEVICE).  matches / match_counts: the out_pairs / out_counts of sgpu_match_batch,
+ * host arrays, set-local {i, j}, concatenated in pair order.  out_models[p] is a row-major 3x3 at
+ * unit Frobenius norm that goes unchanged into sgpu_match_*_guided as H + 9 p or F + 9 p; set a is
+ * the reference's set 1 (H x1 is compared with x2; the Sampson error of x2' F x1).  out_inliers[p]
+ * = its inlier count, out_mask (or NULL) = one byte per match, 1 for an inlier.
+ *
+ * What is computed (csrc/sift_geom.h defines the arithmetic):
+ *  - the inlier test is the guided matcher's own, in its float operation order: homography
+ *    |H x1 - x2| < threshold in both coordinates; fundamental: Sampson error < threshold (squared
+ *    pixels, as fdistmax).  The mask is exactly what the guided test says about the returned
+ *    float matrix, so a guided pass at the same threshold keeps every inlier's geometry;
+ *  - hypothesis t of pair position p draws its minimal sample (4 / 8 matches, without
+ *    replacement) by a counter-based hash of (seed, p, t, draw), solves it in double (H: the
+ *    four-point closed form; F: the eight-point null vector after isotropic normalisation,
+ *    complete pivoting) and rounds to float.  Degenerate samples (a repeated point, three
+ *    collinear points for H, a vanishing pivot for F) are never chosen;
+ *  - the winner has the most inliers, then the lowest t.  `iterations` hypotheses are always
+ *    run: the result is a pure function of the inputs and the seed;
+ *  - a pair with fewer matches than the minimal sample, or without a valid hypothesis, has no
+ *    model: zeros, 0 inliers, a zero mask; fed to a guided call it yields no matches;
+ *  - F is the minimal-sample solution WITHOUT rank-2 enforcement (the Sampson test does not need
+ *    it; a caller that wants epipoles enforces rank 2 itself).  No local refinement.
+ * The number of launches, copies and synchronisations does not depend on npairs;
+ * sgpu_last_timing's times[12] is the call's device time.
+ * SGPU_EINVAL: a pair index outside [0, nsets), decreasing offsets, a negative count, a match
+ * index outside its set (all checked on the host before anything is launched), iterations outside
+ * [1, 65536], an unknown model, NULL out_models / out_inliers (or NULL inputs that are needed). */
+#define SGPU_MODEL_HOMOGRAPHY  0   /* minimal sample 4 */
+#define SGPU_MODEL_FUNDAMENTAL 1   /* minimal sample 8 */
+int sgpu_estimate_batch(sgpu_ctx* ctx, const float* loc /* [set_offsets[nsets]][2] */,
+                        const int64_t* set_offsets, int nsets,
+                        const int* set_pairs /* [npairs][2] */, int npairs,
+                        const int* matches /* [sum counts][2], set-local {i, j} */,
+                        const int* match_counts /* [npairs] */,
+                        int model, float threshold, int iterations, uint32_t seed,
+                        float* out_models /* [npairs][9] */, int* out_inliers /* [npairs] */,
+                        uint8_t* out_mask /* [sum counts] or NULL */, int flags);
+/* sgpu_estimate_batch over the last extract: the sets are the batch's images, the locations x, y
+ * of its device keys (a multi-part batch: the gathered key buffer), so no key crosses PCIe.
+ * Error conditions of sgpu_match_images_guided. */
+int sgpu_estimate_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
+                         const int* matches, const int* match_counts,
+                         int model, float threshold, int iterations, uint32_t seed,
+                         float* out_models, int* out_inliers, uint8_t* out_mask);
+
 /* Timing of the last call: stage times in milliseconds measured with HIP events
  * (SiftGPU::_timing, SiftPyramid.cpp:48-56).  times[0..7] =
  * {upload, pyramid, detect, orientation, expand, descriptor, download, total} of the last
  * extract; times[8] = the last sgpu_match call; times[9] = the feature-list (row scan) part of
- * detect; times[10], [11] = the key and descriptor copies of the last sgpu_copy_features.
+ * detect; times[10], [11] = the key and descriptor copies of the last sgpu_copy_features;
+ * times[12] = the last sgpu_estimate_* call.
  * SiftGPU::_timing[2..8] map them to the reference's slots (siftgpu_api.cpp).  Slots 0-7 and
  * 9-11 read 0 after a one-stream extract / copy made with the stage timing off. */
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n);

@@ -25,6 +25,7 @@
 
 #include "../../include/sgpu.h"
 #include "sift_kernels.h"
+#include "sift_geom.h"
 #include "sift_match_plan.h"
 #include "sift_params.h"
 #include "sift_pyramid_plan.h"
@@ -68,7 +69,7 @@ struct DevBuf {
 // reference's "Detection" and "Feature List" stages, SiftPyramid.cpp:107,123); T_LIST is the
 // row-scan part of it
 enum { T_UPLOAD, T_PYRAMID, T_DETECT, T_ORIENT, T_EXPAND, T_DESC, T_DOWNLOAD, T_TOTAL, T_MATCH,
-       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_N };
+       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_N };
 
 // One part of a batch: consecutive images [img0, img0 + n) with their own stream and buffers.
 struct Part {
@@ -211,6 +212,11 @@ struct sgpu_ctx {
     sgplan::Plan b_hplan;
     bool b_planned = false;                // b_hplan is a call's plan (sgpu_debug_match_plan_stats)
     std::vector<unsigned char> b_tables;   // the tables as uploaded (alive until the call's sync)
+    // geometry estimator (sgpu_estimate_batch): uploaded locations, [pairs][items][matches] in one
+    // upload, the matches' float4 rows, [slots npairs (64-bit)][error flag], [models][inliers], mask
+    DevBuf e_loc, e_plan, e_pts, e_slots, e_out, e_mask;
+    sgeo::Plan e_hplan;
+    std::vector<unsigned char> e_tables, e_result;
     // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
     // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
     DevBuf q_in, q_out, f_u8, f_s8, f_sums;
@@ -547,7 +553,8 @@ int sgpu_ctx_destroy(sgpu_ctx* ctx) {
                       &ctx->m_colpart, &ctx->m_cols, &ctx->m_prune, &ctx->m_s1c,
                       &ctx->b_desc, &ctx->b_s8, &ctx->b_sums, &ctx->b_plan, &ctx->b_part, &ctx->b_dec,
                       &ctx->b_cnt, &ctx->b_out, &ctx->b_loc, &ctx->q_in, &ctx->q_out, &ctx->f_u8, &ctx->f_s8,
-                      &ctx->f_sums, &ctx->c_buf};
+                      &ctx->f_sums, &ctx->c_buf, &ctx->e_loc, &ctx->e_plan, &ctx->e_pts, &ctx->e_slots,
+                      &ctx->e_out, &ctx->e_mask};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i <= T_N; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2412,6 +2419,121 @@ int sgpu_match_images_guided(sgpu_ctx* ctx, const int* image_pairs, int npairs, 
                             ctx->f_sums.as<int>(), ctx->img_off.data(), ctx->batch, image_pairs,
                             npairs, distmax, ratiomax, mutual_best_match, max_match, out_pairs, cap,
                             out_counts, quantises, geo);
+}
+
+// H / F of every pair of a pair list (sift_geom.h is the contract, sift_geom.hip the kernels).
+// loc: device locations (x, y of buffer row r at loc[r * stride]), or host_loc: packed host
+// locations uploaded here, after every argument has been checked.  One table upload
+// ([pairs][items][matches]), one memset, three launches, two device->host copies and one
+// synchronisation, whatever npairs is.
+static int estimate_impl(sgpu_ctx* ctx, const float* loc, int stride, const float* host_loc,
+                         const int64_t* off, int nsets, const int* set_pairs, int npairs,
+                         const int* matches, const int* counts, int model, float threshold,
+                         int iterations, uint32_t seed, float* out_models, int* out_inliers,
+                         uint8_t* out_mask) {
+    hipStream_t st = ctx->stream;
+    sgeo::Plan& plan = ctx->e_hplan;
+    const int prc = sgeo::build_plan(off, nsets, set_pairs, npairs, counts, model, iterations, plan);
+    if (prc == sgeo::kPlanBadArgument)
+        return ctx->fail(SGPU_EINVAL, "bad offsets, pair indices, counts, model or iterations");
+    if (prc != sgeo::kPlanOk) return ctx->fail(SGPU_ERANGE, "estimate batch too large");
+    ctx->timing[T_ESTIMATE] = 0.f;
+    if (npairs == 0) return SGPU_OK;
+    if (!out_models || !out_inliers) return ctx->fail(SGPU_EINVAL, "null outputs");
+    const long long total = plan.total;
+    if (total > 0 && !matches) return ctx->fail(SGPU_EINVAL, "null matches");
+    if (!sgeo::check_matches(off, set_pairs, npairs, matches, counts))
+        return ctx->fail(SGPU_EINVAL, "a match index lies outside its set");
+    if (total > 0 && !loc && !host_loc) return ctx->fail(SGPU_EINVAL, "null locations");
+    if (host_loc && total > 0) {
+        const size_t bytes = (size_t)off[nsets] * 2 * sizeof(float);
+        ALLOCCHK(ctx, ctx->e_loc.ensure(bytes));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->e_loc.p, host_loc, bytes, hipMemcpyHostToDevice, st));
+        loc = ctx->e_loc.as<float>();
+        stride = 2;
+    }
+    const size_t b_pairs = plan.pairs.size() * sizeof(sgeo::PairRec);
+    const size_t b_items = plan.items.size() * sizeof(sgeo::Item);
+    const size_t b_matches = (size_t)total * 2 * sizeof(int);
+    static_assert(sizeof(sgeo::PairRec) % 8 == 0 && sizeof(sgeo::Item) == 8, "the matches stay 8-byte aligned");
+    ctx->e_tables.resize(b_pairs + b_items + b_matches);
+    unsigned char* tb = ctx->e_tables.data();
+    memcpy(tb, plan.pairs.data(), b_pairs);
+    if (b_items) memcpy(tb + b_pairs, plan.items.data(), b_items);
+    if (b_matches) memcpy(tb + b_pairs + b_items, matches, b_matches);
+    // [models npairs x 9 floats][inliers npairs][error flag]
+    const size_t b_models = (size_t)npairs * 9 * sizeof(float);
+    const size_t b_result = b_models + (size_t)(npairs + 1) * sizeof(int);
+    const size_t b_slots = (size_t)npairs * sizeof(unsigned long long);
+    ALLOCCHK(ctx, ctx->e_plan.ensure(ctx->e_tables.size()));
+    ALLOCCHK(ctx, ctx->e_pts.ensure((size_t)std::max<long long>(total, 1) * sizeof(float4)));
+    ALLOCCHK(ctx, ctx->e_slots.ensure(b_slots));
+    ALLOCCHK(ctx, ctx->e_out.ensure(b_result));
+    if (out_mask) ALLOCCHK(ctx, ctx->e_mask.ensure((size_t)std::max<long long>(total, 1)));
+    ctx->e_result.resize(b_result);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->e_plan.p, tb, ctx->e_tables.size(), hipMemcpyHostToDevice, st));
+    const unsigned char* dt = ctx->e_plan.as<unsigned char>();
+    const auto* d_pairs = reinterpret_cast<const sgeo::PairRec*>(dt);
+    const auto* d_items = reinterpret_cast<const sgeo::Item*>(dt + b_pairs);
+    const auto* d_matches = reinterpret_cast<const int*>(dt + b_pairs + b_items);
+    auto* d_slots = ctx->e_slots.as<unsigned long long>();
+    float* d_models = ctx->e_out.as<float>();
+    int* d_inliers = reinterpret_cast<int*>(ctx->e_out.as<unsigned char>() + b_models);
+    int* d_err = d_inliers + npairs;
+    float4* d_pts = ctx->e_pts.as<float4>();
+    HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    HIPCHK(ctx, hipMemsetAsync(d_slots, 0, b_slots, st));
+    HIPCHK(ctx, hipMemsetAsync(d_err, 0, sizeof(int), st));
+    HIPCHK(ctx, sgk::launch_estimate_gather(loc, stride, d_pairs, npairs, d_matches, total, d_pts, st));
+    HIPCHK(ctx, sgk::launch_estimate_pairs(d_pts, d_pairs, d_items, (int)plan.items.size(), model,
+                                           threshold, iterations, seed, d_slots, st));
+    HIPCHK(ctx, sgk::launch_estimate_finish(d_pts, d_pairs, npairs, model, threshold, seed, d_slots,
+                                            d_models, d_inliers,
+                                            out_mask ? ctx->e_mask.as<uint8_t>() : nullptr, d_err, st));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[2], st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->e_result.data(), ctx->e_out.p, b_result, hipMemcpyDeviceToHost, st));
+    if (out_mask && total > 0)
+        HIPCHK(ctx, hipMemcpyAsync(out_mask, ctx->e_mask.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&ctx->timing[T_ESTIMATE], ctx->ev[1], ctx->ev[2]);
+    memcpy(out_models, ctx->e_result.data(), b_models);
+    memcpy(out_inliers, ctx->e_result.data() + b_models, (size_t)npairs * sizeof(int));
+    int err = 0;
+    memcpy(&err, ctx->e_result.data() + b_models + (size_t)npairs * sizeof(int), sizeof(int));
+    if (err) return ctx->fail(SGPU_ENODEV, "estimate: a regenerated winner's inlier count differs from its score");
+    return SGPU_OK;
+}
+
+int sgpu_estimate_batch(sgpu_ctx* ctx, const float* loc, const int64_t* set_offsets, int nsets,
+                        const int* set_pairs, int npairs, const int* matches,
+                        const int* match_counts, int model, float threshold, int iterations,
+                        uint32_t seed, float* out_models, int* out_inliers, uint8_t* out_mask,
+                        int flags) {
+    if (!ctx) return SGPU_EINVAL;
+    if (nsets < 0 || npairs < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad estimate batch arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const bool dev = (flags & SGPU_INPUT_DEVICE) != 0;
+    return estimate_impl(ctx, dev ? loc : nullptr, 2, dev ? nullptr : loc, set_offsets, nsets,
+                         set_pairs, npairs, matches, match_counts, model, threshold, iterations, seed,
+                         out_models, out_inliers, out_mask);
+}
+
+int sgpu_estimate_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, const int* matches,
+                         const int* match_counts, int model, float threshold, int iterations,
+                         uint32_t seed, float* out_models, int* out_inliers, uint8_t* out_mask) {
+    if (!ctx) return SGPU_EINVAL;
+    if (npairs < 0) return ctx->fail(SGPU_EINVAL, "bad estimate arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the states sgpu_match_images_guided refuses (feature_u8), without its quantisation
+    if (ctx->batch <= 0 || ctx->img_off.empty())
+        return ctx->fail(SGPU_EINVAL, "no extracted batch to estimate on");
+    if (!ctx->opt.descriptors) return ctx->fail(SGPU_EINVAL, "descriptors disabled (-sd)");
+    const float* keys = nullptr;
+    const int rc = sgpu_device_features(ctx, &keys, nullptr, nullptr);   // (gathers a multi-part batch)
+    if (rc != SGPU_OK) return rc;
+    return estimate_impl(ctx, keys, 4, nullptr, ctx->img_off.data(), ctx->batch, image_pairs, npairs,
+                         matches, match_counts, model, threshold, iterations, seed, out_models,
+                         out_inliers, out_mask);
 }
 
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n) {

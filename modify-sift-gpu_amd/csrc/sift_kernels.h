@@ -382,6 +382,11 @@ struct Side;
 struct FinishPanel;
 struct PairRec;
 }  // namespace sgplan
+// the estimator's tables (sift_geom.h)
+namespace sgeo {
+struct PairRec;
+struct Item;
+}  // namespace sgeo
 
 namespace sgk {
 // float descriptors d [n][128] -> u8 by the rule of sgpu_quantize_descriptors, and in the same
@@ -412,4 +417,24 @@ hipError_t launch_match_pairs_finish(const Top2* part, const sgplan::Side* sides
 hipError_t launch_match_pairs_compact(const int* dec, const sgplan::PairRec* pairs, int npairs,
                                       int max_match, long long cap, int* counts, long long* offs,
                                       int* out, hipStream_t stream);
+
+// ---- geometry estimation of matched pairs (sift_geom.hip; the arithmetic is sift_geom.h's) ----
+// One thread per match of the concatenated list: pts[k] = (x1, y1, x2, y2) of match k, its pair
+// found by a binary search over pairs[].moff.  loc as launch_match_pairs_guided's.
+hipError_t launch_estimate_gather(const float* loc, int loc_stride, const sgeo::PairRec* pairs,
+                                  int npairs, const int* matches, long long total, float4* pts,
+                                  hipStream_t stream);
+// One workgroup per work item (pair, block of 256 hypotheses), a lane per hypothesis: sample,
+// solve, count the inliers over the pair's matches; the block's best key (sgeo::hyp_key) goes to
+// slots[pair] by one atomic max.  slots must be cleared beforehand.
+hipError_t launch_estimate_pairs(const float4* pts, const sgeo::PairRec* pairs,
+                                 const sgeo::Item* items, int nitems, int model, float threshold,
+                                 int iterations, uint32_t seed, unsigned long long* slots,
+                                 hipStream_t stream);
+// One workgroup per pair: the winner regenerated from its t -> models[p][9], the mask of its
+// inliers (mask may be null), inliers[p]; *err is set when a count differs from the slot's.
+hipError_t launch_estimate_finish(const float4* pts, const sgeo::PairRec* pairs, int npairs,
+                                  int model, float threshold, uint32_t seed,
+                                  const unsigned long long* slots, float* models, int* inliers,
+                                  uint8_t* mask, int* err, hipStream_t stream);
 }  // namespace sgk

@@ -38,6 +38,7 @@ C_API = [
     "sgpu_match_batch", "sgpu_match_images", "sgpu_debug_match_plan_stats",
     "sgpu_debug_set_duo_strips", "sgpu_debug_pyramid_plan", "sgpu_debug_set_feature_queue",
     "sgpu_match_batch_guided", "sgpu_match_images_guided",
+    "sgpu_estimate_batch", "sgpu_estimate_images",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -124,6 +125,10 @@ def lib():
         L.sgpu_match_images_guided.argtypes = [vp, vp, c.c_int, vp, vp, c.c_float, c.c_float,
                                                c.c_float, c.c_float, c.c_int, c.c_int, vp,
                                                c.c_int64, vp]
+        L.sgpu_estimate_batch.argtypes = [vp, vp, vp, c.c_int, vp, c.c_int, vp, vp, c.c_int,
+                                          c.c_float, c.c_int, c.c_uint32, vp, vp, vp, c.c_int]
+        L.sgpu_estimate_images.argtypes = [vp, vp, c.c_int, vp, vp, c.c_int, c.c_float, c.c_int,
+                                           c.c_uint32, vp, vp, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -648,6 +653,67 @@ class SiftContext:
                 distmax, ratiomax, hdistmax, fdistmax, mbm, mm, out.ctypes.data, cp,
                 counts.ctypes.data)
         return self._pair_results(call, pairs, sizes, max_match, cap)
+
+    MODELS = {"H": 0, "F": 1}   # SGPU_MODEL_HOMOGRAPHY / SGPU_MODEL_FUNDAMENTAL
+
+    def _estimate(self, call, pairs, matches, model, threshold, iterations, seed):
+        """Common part of estimate_batch / estimate_images: the pair list and the per-pair [m, 2]
+        match arrays go down concatenated; (models [npairs][3][3] float32, inliers [npairs]
+        int32, masks: one bool array per pair) come back."""
+        if model not in self.MODELS:
+            raise ValueError(f'model must be "H" or "F", got {model!r}')
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        npairs = len(pr)
+        if len(matches) != npairs:
+            raise ValueError(f"{npairs} pairs but {len(matches)} match arrays")
+        ms = [np.ascontiguousarray(m, np.int32).reshape(-1, 2) for m in matches]
+        counts = np.array([len(m) for m in ms], np.int32).reshape(npairs)
+        cat = (np.concatenate(ms) if npairs else np.zeros((0, 2), np.int32)).astype(np.int32)
+        cat = np.ascontiguousarray(cat)
+        total = len(cat)
+        models = np.zeros((max(npairs, 1), 9), np.float32)
+        inliers = np.zeros(max(npairs, 1), np.int32)
+        mask = np.zeros(max(total, 1), np.uint8)
+        rc = call(pr.ctypes.data if npairs else None, npairs, cat.ctypes.data if total else None,
+                  counts.ctypes.data if npairs else None, self.MODELS[model], float(threshold),
+                  int(iterations), int(seed) & 0xFFFFFFFF, models.ctypes.data, inliers.ctypes.data,
+                  mask.ctypes.data)
+        self._check(rc, "estimate")
+        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        masks = [mask[offs[p]:offs[p + 1]].astype(bool) for p in range(npairs)]
+        return models[:npairs].reshape(npairs, 3, 3).copy(), inliers[:npairs].copy(), masks
+
+    def estimate_batch(self, loc: np.ndarray, offsets, pairs, matches, model="H", threshold=2.0,
+                       iterations=512, seed=0, device_ptr=None):
+        """One H or F per set pair from its matches (sgpu_estimate_batch): loc [rows][2] (x, y) of
+        the sets of match_batch, pairs [(a, b), ...], matches = the list of [m, 2] arrays that
+        match_batch returned for them.  model "H": |H x1 - x2| < threshold in both coordinates;
+        "F": Sampson error < threshold (squared pixels), no rank-2 enforcement.  Returns (models
+        [npairs][3][3] float32 at unit Frobenius norm, ready for match_batch_guided; inlier counts
+        [npairs]; one bool mask per pair).  A pair without a model has zeros.  device_ptr: the
+        int device address of the locations, read in place (SGPU_INPUT_DEVICE; loc is ignored)."""
+        off = np.ascontiguousarray(offsets, np.int64)
+        nsets = len(off) - 1
+        if device_ptr is not None:
+            ptr, flags = ctypes.c_void_p(device_ptr), SGPU_INPUT_DEVICE
+        else:
+            lc = np.ascontiguousarray(loc, np.float32)
+            if lc.ndim != 2 or lc.shape[1] != 2 or nsets < 0 or (len(off) and off[-1] > len(lc)):
+                raise ValueError(f"locations must be [rows][2] covering the offsets, got {lc.shape}")
+            ptr, flags = (lc.ctypes.data if len(lc) else None), SGPU_INPUT_HOST
+
+        def call(pr, npairs, cat, counts, mdl, thr, it, sd, models, inliers, mask):
+            return lib().sgpu_estimate_batch(self._ctx, ptr, off.ctypes.data, nsets, pr, npairs, cat,
+                                             counts, mdl, thr, it, sd, models, inliers, mask, flags)
+        return self._estimate(call, pairs, matches, model, threshold, iterations, seed)
+
+    def estimate_images(self, pairs, matches, model="H", threshold=2.0, iterations=512, seed=0):
+        """estimate_batch over the last extract (sgpu_estimate_images): pairs of its images, matches
+        as match_images returned them; the locations are the batch's device keys and stay in HBM."""
+        def call(pr, npairs, cat, counts, mdl, thr, it, sd, models, inliers, mask):
+            return lib().sgpu_estimate_images(self._ctx, pr, npairs, cat, counts, mdl, thr, it, sd,
+                                              models, inliers, mask)
+        return self._estimate(call, pairs, matches, model, threshold, iterations, seed)
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
