@@ -224,17 +224,8 @@ hipError_t launch_copy_out(const float4* keys, const float* desc, const uint32_t
                            int64_t* hrec, hipStream_t stream);
 
 // Descriptors (+ normalisation) of the expanded features; n_feat_cap sizes the grid (one wave
-// per feature), the kernel grid-strides over *n_feat_dev.  out_index (optional): feature e's
-// descriptor goes to row out_index[e].  rect: the rectangle descriptor of keys given with
-// keys_have_orientation == -1 (feat = (x, y, width, height) in octave coordinates).
-// exact: the reference's per-bin fma order and the oracle's transcendentals (bit-identical to the
-// oracle; the test mode); otherwise the relaxed-order pixel-parallel kernel k_descriptor_flat
-// (L2 ~1e-6 from the oracle), or with dual the round-4 dual-cell kernel (A/B).  wide: the
-// relaxed-order kernel with a workgroup of 4 waves per feature (k_descriptor_wide, for few
-// features; the grid is then one workgroup per feature up to n_feat_cap) -- the same bits.
-// host (wide only): keys[e], descriptor row e (e < cap) and the rec_n (<= 256) int64 words of rec
-// also to page-locked host memory, in place of a launch_copy_out after the kernel.
-// queue: k_descriptor_flat in its persistent form (ignored by the other kernels) -- the same bits.
+// per feature), the kernel grid-strides over *n_feat_dev.  All of DescriptorForm unset: the
+// relaxed-order pixel-parallel kernel k_descriptor_flat (L2 ~1e-6 from the oracle).
 struct HostCopy {
     const float4* keys = nullptr;
     const int64_t* rec = nullptr;
@@ -244,12 +235,25 @@ struct HostCopy {
     float* hdesc = nullptr;
     int64_t* hrec = nullptr;
 };
+struct DescriptorForm {
+    const int* out_index = nullptr;   // feature e's descriptor goes to row out_index[e]
+    bool rect = false;    // the rectangle descriptor of keys given with keys_have_orientation == -1
+                          // (feat = (x, y, width, height) in octave coordinates)
+    bool exact = false;   // the reference's per-bin fma order and the oracle's transcendentals
+                          // (bit-identical to the oracle; the test mode)
+    bool dual = false;    // the round-4 dual-cell kernel (A/B)
+    bool wide = false;    // the relaxed-order kernel with a workgroup of 4 waves per feature
+                          // (k_descriptor_wide, for few features; the grid is then one workgroup
+                          // per feature up to n_feat_cap) -- the same bits
+    // wide only: keys[e], descriptor row e (e < cap) and the rec_n (<= 256) int64 words of rec
+    // also to page-locked host memory, in place of a launch_copy_out after the kernel
+    const HostCopy* host = nullptr;
+    // k_descriptor_flat in its persistent form (ignored by the other kernels) -- the same bits
+    const FeatureQueue* queue = nullptr;
+};
 hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* feat_info,
                              const uint32_t* n_feat_dev, int n_feat_cap, const FeatureParams& fp,
-                             float* desc, hipStream_t stream, const int* out_index = nullptr,
-                             bool rect = false, bool exact = false, bool dual = false,
-                             bool wide = false, const HostCopy* host = nullptr,
-                             const FeatureQueue* queue = nullptr);
+                             float* desc, const DescriptorForm& form, hipStream_t stream);
 
 // Caller-supplied keypoints: strongest orientation into feat[e].w (num_orientation != 0, else
 // 0) and the image-coordinate key at keys_out[index[e]].
@@ -283,16 +287,24 @@ constexpr int kDistTable = 262145;
 struct Top2 { int max, idx, second; };
 // dst = src xor 0x80 (u8 -> s8 descriptors, the operands of the i8 MFMA), n descriptors
 hipError_t launch_to_s8(const uint8_t* src, int n, uint8_t* dst, hipStream_t stream);
-// s[i] = scale * sum_k d[i][k] + bias
-hipError_t launch_rowsums(const uint8_t* d, int n, int* s, int scale, int bias, hipStream_t stream);
-// both at once, for one set: dst = s8 form, sums[i] = scale * sum_k src[i][k] + bias (sums may
-// be null), zero[0 .. nzero) = 0, and ctp (optional, n + match_ct_pad() entries) the biased
-// column terms of a raw launch_match_rows with this set as B
-// ctfill (optional, n + match_ct_pad() entries): set to the column term of a missing column, so
-// that a launch_prune_set output over it reads as padded past its device-side count
-hipError_t launch_prep_set(const uint8_t* src, int n, uint8_t* dst, int* sums, int scale,
-                           int bias, int* zero, int nzero, hipStream_t stream,
-                           int* ctp = nullptr, int* ctfill = nullptr);
+// the same conversion of one set (dst = the s8 form of src's n descriptors) with, in the same
+// launch, whichever of these are set
+struct PrepSet {
+    const uint8_t* src;
+    int n;
+    uint8_t* dst;
+    int* sums = nullptr;     // sums[i] = scale * sum_k src[i][k] + bias
+    int scale = 128;
+    int bias = 0;
+    int* zero = nullptr;     // zero[0 .. nzero) = 0
+    int nzero = 0;
+    int* ctp = nullptr;      // (n + match_ct_pad() entries) the biased column terms of a raw
+                             // launch_match_rows with this set as B
+    int* ctfill = nullptr;   // (n + match_ct_pad() entries) set to the column term of a missing
+                             // column, so that a launch_prune_set output over it reads as padded
+                             // past its device-side count
+};
+hipError_t launch_prep_set(const PrepSet& p, hipStream_t stream);
 int match_ct_pad();
 // column chunks of a row launch: dma = the launch runs k_match_raw (raw with ctp), whose split
 // is its own cost model (sift_match.hip chunks_for)
@@ -300,25 +312,37 @@ int match_chunks(int nA, int nB, bool dma = false);
 // part[chunk][nA]: per-row top-2 of (A_i . B_j + col_term[j]) over each column chunk, with
 // col_term[j] = 128 * sum(B_j) - 2^21 formed in the kernel from the staged bytes.  A and B are
 // the s8 forms of the descriptor sets (launch_to_s8).
-// row_side: equal maxima resolve as RowMatch_Kernel does (A = set 1); else in column order.
-// With a mask (launch_guided_mask, this side's lane records): the guided values
-// (k_match_rows<true>).
-// colpart != nullptr (row_side only; row_term = 128 * sum(A rows)): the fused mutual form --
-// colpart[panel][nB] also receives every 128-row panel's column-side (max, row, second) of
-// (dot - column term) (guided: of the guided value), for launch_match_cols.
-// raw (plain matching with ratiomax <= 1 only): values folded without keys; part.idx is then
-// (tile + lane) and k_match_finish recovers the column (pass raw_A / raw_B to it).
-// ctp (raw only; launch_prep_set of B): the LDS-DMA kernel k_match_raw, same partials.
-// amap / an (plain matching only): the rows are A[amap[r]] for r < *an (a count on the device,
-// at most nA); the launch covers every count and the split is chunks_for(*an, nB, dma), which
-// launch_match_finish with ColumnList{map, count, dma} derives again.  part needs
-// match_part_bound(nA, nB, dma) entries.
-hipError_t launch_match_rows(const uint8_t* A, int nA, const uint8_t* B, int nB,
-                             int chunks, Top2* part, hipStream_t stream,
-                             const uint8_t* mask, bool row_side, const int* row_term = nullptr,
-                             Top2* colpart = nullptr, bool raw = false,
-                             const int* amap = nullptr, const int* an = nullptr,
-                             const int* ctp = nullptr, const int* bn = nullptr);
+struct MatchRows {
+    const uint8_t* A;
+    int nA;
+    const uint8_t* B;
+    int nB;
+    int chunks;
+    Top2* part;
+    // equal maxima resolve as RowMatch_Kernel does (A = set 1); false: in column order
+    bool row_side = true;
+    // this side's lane records of launch_guided_mask: the guided values (k_match_rows<true>)
+    const uint8_t* mask = nullptr;
+    // colpart set (row_side only; row_term = 128 * sum(A rows)): the fused mutual form --
+    // colpart[panel][nB] also receives every 128-row panel's column-side (max, row, second) of
+    // (dot - column term) (guided: of the guided value), for launch_match_cols
+    const int* row_term = nullptr;
+    Top2* colpart = nullptr;
+    // plain matching with ratiomax <= 1 only: values folded without keys; part.idx is then
+    // (tile + lane) and k_match_finish recovers the column (pass raw_A / raw_B to it)
+    bool raw = false;
+    // plain matching only: the rows are A[amap[r]] for r < *an (a count on the device, at most
+    // nA); the launch covers every count and the split is chunks_for(*an, nB, dma), which
+    // launch_match_finish with ColumnList{map, count, dma} derives again.  part needs
+    // match_part_bound(nA, nB, dma) entries.
+    const int* amap = nullptr;
+    const int* an = nullptr;
+    // raw only (launch_prep_set of B): the LDS-DMA kernel k_match_raw, same partials
+    const int* ctp = nullptr;
+    // k_match_raw over compacted rows only: B's count on the device (launch_prune_set)
+    const int* bn = nullptr;
+};
+hipError_t launch_match_rows(const MatchRows& r, hipStream_t stream);
 size_t match_part_bound(int nA, int nB, bool dma = false);
 int match_panels(int nA);
 // Column decisions from the panels' partials: col_term[j] = 128 * sum(B_j) - 2^21 (guided: 0).
@@ -334,10 +358,6 @@ size_t guided_mask_bytes(int nA, int nB);
 hipError_t launch_guided_mask(const float* loc1, int n1, const float* loc2, int n2,
                               const GuidedParams& gp, uint8_t* rec1, uint8_t* rec2,
                               hipStream_t stream);
-// merge chunks, add row_term (nullptr: none), apply distmax / ratiomax -> out[i] = matched
-// index or -1
-// raw_A / raw_B / nB: the u8 sets of a raw launch_match_rows (A = this side's rows; nB = the
-// other side's count, also needed with cl.map)
 // The column side of a mutual match only needs the columns some row matched (the host's check
 // reads match2[j] only for j = match1[i] >= 0).  ColumnList, row side: flag (nB ints, zeroed)
 // and count (zeroed) set -> each matched column is appended once to list.  Column side: map =
@@ -366,11 +386,27 @@ struct ColumnList {
 hipError_t launch_prune_set(const int* rmax, const int* ntau, int n, const uint8_t* s8,
                             const int* ct, uint8_t* s8c, int* ctc, int* mapc, int* countc,
                             hipStream_t stream);
-hipError_t launch_match_finish(const Top2* part, int n, int chunks, const int* row_term,
-                               const float* dist, float distmax, float ratiomax, int* out,
-                               Top2* best, hipStream_t stream, bool row_side,
-                               const uint8_t* raw_A = nullptr, const uint8_t* raw_B = nullptr,
-                               int nB = 0, ColumnList cl = ColumnList{});
+// merge chunks, add row_term (nullptr: none), apply distmax / ratiomax -> out[i] = matched
+// index or -1
+struct MatchFinish {
+    const Top2* part;
+    int n;
+    int chunks;
+    const int* row_term;
+    const float* dist;
+    float distmax;
+    float ratiomax;
+    int* out;
+    bool row_side = true;
+    Top2* best = nullptr;             // (optional) every row's merged (max, idx, second)
+    // the u8 sets of a raw launch_match_rows (A = this side's rows); nB = the other side's
+    // count, also needed with cl.map
+    const uint8_t* raw_A = nullptr;
+    const uint8_t* raw_B = nullptr;
+    int nB = 0;
+    ColumnList cl{};
+};
+hipError_t launch_match_finish(const MatchFinish& f, hipStream_t stream);
 
 }  // namespace sgk
 

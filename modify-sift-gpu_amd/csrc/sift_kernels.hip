@@ -3698,9 +3698,11 @@ hipError_t launch_orient_keys(const float* pyr, float4* feat, const int2* feat_i
 
 hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* feat_info,
                              const uint32_t* n_feat_dev, int n_feat_cap, const FeatureParams& fp,
-                             float* desc, hipStream_t stream, const int* out_index,
-                             bool rect, bool exact, bool dual, bool wide, const HostCopy* host,
-                             const FeatureQueue* queue) {
+                             float* desc, const DescriptorForm& form, hipStream_t stream) {
+    const int* out_index = form.out_index;
+    const bool rect = form.rect, exact = form.exact, dual = form.dual, wide = form.wide;
+    const HostCopy* host = form.host;
+    const FeatureQueue* queue = form.queue;
     if (n_feat_cap <= 0) return hipSuccess;
     if (host && (!wide || exact || rect || dual || host->rec_n < 0 || host->rec_n > 256 ||
                  !host->hkeys || !host->hrec || !host->keys || !host->rec))

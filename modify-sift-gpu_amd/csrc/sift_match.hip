@@ -65,18 +65,6 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
     return max(min(a, b), min(max(a, b), c));
 }
 
-__global__ __launch_bounds__(256) void k_rowsum(const uint8_t* __restrict__ d, int n,
-                                                int* __restrict__ s, int scale, int bias) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= n) return;
-    const uint16_t v = reinterpret_cast<const uint16_t*>(d + (size_t)i * 128)[lane];
-    int t = (v & 0xff) + (v >> 8);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    if (lane == 0) s[i] = scale * t + bias;
-}
-
 // Column chunks of one launch: ~4096 workgroups (about 5 per resident slot at 3 per CU) so
 // that the last wave of workgroups is a small tail; each chunk at least two tiles wide.  Also
 // evaluated on the device for a row count that only the device knows (compacted rows).
@@ -1274,23 +1262,15 @@ hipError_t launch_to_s8(const uint8_t* src, int n, uint8_t* dst, hipStream_t str
     return hipGetLastError();
 }
 
-hipError_t launch_prep_set(const uint8_t* src, int n, uint8_t* dst, int* sums, int scale,
-                           int bias, int* zero, int nzero, hipStream_t stream, int* ctp,
-                           int* ctfill) {
+hipError_t launch_prep_set(const PrepSet& p, hipStream_t stream) {
+    const int n = p.n, nzero = p.nzero;
     if (n <= 0 && nzero <= 0) return hipSuccess;
     const size_t n16 = (size_t)std::max(n, 0) * 8;
     const size_t work = std::max(n16, (size_t)std::max(nzero, 0));
     const unsigned grid = (unsigned)std::min<size_t>((work + 255) / 256, 4096);
     hipLaunchKernelGGL(k_prep_set, dim3(grid), dim3(256), 0, stream,
-                       reinterpret_cast<const uint4*>(src), n16, reinterpret_cast<uint4*>(dst),
-                       sums, scale, bias, zero, nzero, ctp, std::max(n, 0), ctfill);
-    return hipGetLastError();
-}
-
-hipError_t launch_rowsums(const uint8_t* d, int n, int* out, int scale, int bias,
-                          hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rowsum, dim3((n + 3) / 4), dim3(256), 0, stream, d, n, out, scale, bias);
+                       reinterpret_cast<const uint4*>(p.src), n16, reinterpret_cast<uint4*>(p.dst),
+                       p.sums, p.scale, p.bias, p.zero, nzero, p.ctp, std::max(n, 0), p.ctfill);
     return hipGetLastError();
 }
 
@@ -1323,11 +1303,12 @@ static unsigned match_grid_bound(int nA, int nB, bool dma) {
 
 int match_panels(int nA) { return (nA + kPanel - 1) / kPanel; }
 
-hipError_t launch_match_rows(const uint8_t* A, int nA, const uint8_t* B, int nB,
-                             int chunks, Top2* part, hipStream_t stream,
-                             const uint8_t* mask, bool row_side, const int* row_term,
-                             Top2* colpart, bool raw, const int* amap, const int* an,
-                             const int* ctp, const int* bn) {
+hipError_t launch_match_rows(const MatchRows& r, hipStream_t stream) {
+    const uint8_t *A = r.A, *B = r.B, *mask = r.mask;
+    const int nA = r.nA, nB = r.nB, chunks = r.chunks;
+    Top2 *part = r.part, *colpart = r.colpart;
+    const bool row_side = r.row_side, raw = r.raw;
+    const int *row_term = r.row_term, *amap = r.amap, *an = r.an, *ctp = r.ctp, *bn = r.bn;
     if (raw && (mask || colpart)) return hipErrorInvalidValue;
     if (nA <= 0 || nB <= 0) return hipSuccess;
     if (colpart && (!row_term || !row_side)) return hipErrorInvalidValue;
@@ -1388,20 +1369,18 @@ hipError_t launch_match_cols(const Top2* colpart, int n, int panels, const int* 
     return hipGetLastError();
 }
 
-hipError_t launch_match_finish(const Top2* part, int n, int chunks, const int* row_term,
-                               const float* dist, float distmax, float ratiomax, int* out,
-                               Top2* best, hipStream_t stream, bool row_side,
-                               const uint8_t* raw_A, const uint8_t* raw_B, int nB,
-                               ColumnList cl) {
+hipError_t launch_match_finish(const MatchFinish& f, hipStream_t stream) {
+    const int n = f.n;
+    const uint8_t *raw_A = f.raw_A, *raw_B = f.raw_B;
+    const ColumnList& cl = f.cl;
     if (n <= 0) return hipSuccess;
     if ((cl.map && !cl.count) || (cl.flag && (!cl.list || !cl.count || cl.map))) return hipErrorInvalidValue;
     if ((cl.rmax != nullptr) != (cl.ntau != nullptr) || (cl.ntau && (!cl.flag || !raw_A)) ||
         (cl.bmap != nullptr) != (cl.bn != nullptr) || (cl.bn && (!cl.map || !raw_A)))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_match_finish, dim3((n + kFinishRows - 1) / kFinishRows), dim3(kFinishThreads), 0,
-                       stream, part, n,
-                       chunks, row_term, dist, distmax, ratiomax, out, best, row_side ? 1 : 0,
-                       raw_A, raw_B, nB, cl);
+                       stream, f.part, n, f.chunks, f.row_term, f.dist, f.distmax, f.ratiomax, f.out,
+                       f.best, f.row_side ? 1 : 0, raw_A, raw_B, f.nB, cl);
     return hipGetLastError();
 }
 

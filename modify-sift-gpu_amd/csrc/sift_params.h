@@ -7,7 +7,7 @@
 //   * octave geometry      PyramidCU.cpp:89-271 (InitPyramid / ResizePyramid), width padding
 //                          wa = ((w+3)/4)*4 at PyramidCU.cpp:242, TruncateWidthCU GLTexImage.h:125
 //   * global defaults      GlobalUtil.cpp:50-135
-// Used by the product host code (sgpu_capi) and by the CPU oracle, so both see the same taps.
+// Used by the product host code (the sgpu_*.cpp files) and by the CPU oracle, so both see the same taps.
 #pragma once
 #include <cmath>
 #include <vector>

@@ -1,5 +1,5 @@
 // sift_pyramid_plan.h -- the launch schedule of the Gaussian pyramid.  No HIP
-// include: the library (enqueue_part, sgpu_capi.cpp) and the CPU check
+// include: the library (enqueue_part, sgpu_extract.cpp) and the CPU check
 // (tests/abi/pyramid_plan_check.cpp) both run plan_pyramid(), a pure function from what the rules
 // read -- the level filters' geometry, the rule switches, and which level combinations have a
 // compiled kernel -- to the ordered list of launches.  The library walks that list; nothing else

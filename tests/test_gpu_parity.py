@@ -642,7 +642,7 @@ def test_simplesift_replica(tmp_path):
 
 @pytest.mark.parametrize("flags", [1, 2])
 def test_batch_parts_match_single_part(gpu_ctx, flags):
-    """The batch split into 2 / 4 parts on separate streams (sgpu_capi.cpp extract_impl) gives
+    """The batch split into 2 / 4 parts on separate streams (sgpu_extract.cpp extract_impl) gives
     the single-part results image by image, including the gathered device arrays."""
     imgs = np.stack([synth_image(320, 240, 900 + i) for i in range(7)])
     gpu_ctx.set_options(default_options())
