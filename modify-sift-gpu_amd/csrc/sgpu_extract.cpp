@@ -509,7 +509,7 @@ static int check_extract_args(sgpu_ctx* ctx, const void* images, bool is_f32, in
 static int extract_body(sgpu_ctx* ctx, const void* images, bool is_f32, int n, int w, int h,
                         int stride, int flags, int color) {
     // a caller's float image may hold any range; u8, colour and the library's own conversions of
-    // them lie in [0, 1] (the descriptor's 32-bit sums rely on it, sift_kernels.hip flat_narrow)
+    // them lie in [0, 1] (FeatureParams::unit_input; the shipped 64-bit descriptor sums hold for both)
     ctx->unit_input = !is_f32;
     const bool staged = (flags & SGPU_INPUT_STAGED) != 0;
     const int channels = color == SGPU_RGB || color == SGPU_BGR ? 3 : color ? 4 : 1;

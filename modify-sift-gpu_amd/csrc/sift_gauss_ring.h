@@ -42,7 +42,7 @@ __device__ __forceinline__ int ring_block(int bid, int nb) {
     return xcd < r ? xcd * (q + 1) + k : r * (q + 1) + (xcd - r) * q + k;
 }
 
-// p / 255 correctly rounded on a pair (u8_to_unit of sift_kernels.hip, packed: the same three
+// p / 255 correctly rounded on a pair (u8_to_unit of sift_level.hip, packed: the same three
 // IEEE operations per element)
 __device__ __forceinline__ f2v u8_pair_to_unit(uint32_t a, uint32_t b) {
     const float c = 1.0f / 255.0f;

@@ -1,4 +1,22 @@
-// sift_kernels.h -- launch interface of the gfx950 SIFT kernels (sift_kernels.hip).
+// sift_kernels.h -- launch interface of the gfx950 (MI355X / CDNA4) kernels of the SIFT hot path:
+// sift_level.hip (Gaussian levels, input conversion), sift_detect.hip (extrema, scans, limits),
+// sift_orient.hip (orientation, expansion), sift_kernels.hip (descriptors), and the files
+// named at their sections below.
+//
+// Reference semantics: SiftGPU/ProgramCU.cu (kernels) and SiftGPU/PyramidCU.cpp (stage order).
+// The structure is MI355X-first, not a translation:
+//   * one launch per (octave, level) covers the whole image batch (grid.z = image);
+//   * the separable Gaussian is one fused kernel (H pass into an LDS tile, V pass from LDS),
+//     8 B/px of HBM traffic per level instead of the reference's 16, with the next octave's
+//     2x downsample written from the same tile;
+//   * DoG and gradient images are never stored: the extremum kernel forms the 5 DoG planes of
+//     an octave in LDS from the 6 Gaussian planes, and the orientation / descriptor kernels
+//     evaluate gradients from the Gaussian level on the fly;
+//   * keypoint compaction is a 1-bit-per-pixel mask written with wave ballots plus per-row
+//     counts; one exclusive scan over rows gives every keypoint its slot in the reference's
+//     (image, octave, level, row, column) order -- no histogram pyramid, no host round trips.
+// Floating-point conventions are those of oracle/sift_oracle.cpp (fma contractions written
+// out, transcendentals from sift_math.h); the build uses -ffp-contract=off.
 //
 // All launchers are asynchronous on `stream` and take device pointers.  Images of one batch
 // share one geometry; every kernel covers the whole batch in one launch (grid.z / flat index).

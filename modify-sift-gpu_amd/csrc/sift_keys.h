@@ -1,4 +1,4 @@
-// sift_keys.h -- device-side keypoint helpers shared by the product kernels (sift_kernels.hip)
+// sift_keys.h -- device-side keypoint helpers shared by the product kernels (sift_detect.hip, sift_orient.hip)
 // and the test-hook library's candidate dump (sgpu_debug.hip): ComputeKEY_Kernel's state machine
 // (key_test) and the (image, octave, level, row, column) of a scanned keypoint slot (locate,
 // key_at).  Included after sift_kernels.h and sift_math.h (`using namespace sgm`).

@@ -80,7 +80,7 @@ def test_descriptor_histograms_are_lds_only():
 def test_single_image_kernels_use_no_scratch():
     with tempfile.TemporaryDirectory() as td:
         meta = {}
-        for src in ("sift_kernels.hip.o", "sift_gauss_tile.hip.o"):
+        for src in ("sift_kernels.hip.o", "sift_detect.hip.o", "sift_gauss_tile.hip.o"):
             obj = os.path.join(BUILD, src)
             _need(obj)
             meta.update(_kernel_meta(_code_object(obj, td)))

@@ -307,7 +307,7 @@ def _round_f32(fr):
 
 def test_u8_scale_is_exact_division():
     """The Gaussian kernel's u8 ingest computes p/255.0f as q = p*(1/255), q + fma(fma(-q, 255,
-    p), 1/255, q) (sift_kernels.hip u8_to_unit); exhaustively equal to the IEEE quotient."""
+    p), 1/255, q) (sift_level.hip u8_to_unit); exhaustively equal to the IEEE quotient."""
     from fractions import Fraction
     c = np.float32(1.0) / np.float32(255.0)
     for p in range(256):
