@@ -205,7 +205,10 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
                     mx = fmax_(mx, fmax_(fmax_(hx0[m][k], hx1[m][k]), hx2[m][k]));
                     mn = fmin_(mn, fmin_(fmin_(hn0[m][k], hn1[m][k]), hn2[m][k]));
                 }
-                const bool cand = row_ok && out_col[k] && fabs_(v) > fp.t0 && (v >= mx || v <= mn);
+                // (stated as the negation of ComputeKEY's exits: a NaN v takes none of them and is
+                // a candidate in the reference, and mx / mn include v, so they are never NaN for
+                // another v)
+                const bool cand = row_ok && out_col[k] && !(fabs_(v) <= fp.t0) && !(v < mx && v > mn);
                 const unsigned long long bal = __ballot(cand);
                 if (cand) {
                     const int pos = ncand + __builtin_amdgcn_mbcnt_hi(
@@ -365,7 +368,8 @@ __global__ __launch_bounds__(256) void k_extrema_tile(const float* __restrict__ 
                 mx = fmax_(mx, fmax_(fmax_(hx[m][i], hx[m][i + 1]), hx[m][i + 2]));
                 mn = fmin_(mn, fmin_(fmin_(hn[m][i], hn[m][i + 1]), hn[m][i + 2]));
             }
-            if (row_ok && col_ok && fabs_(v) > fp.t0 && (v >= mx || v <= mn)) pend |= 1u << (i * NJ + j);
+            // (the negation of ComputeKEY's exits, which a NaN v does not take: k_extrema_wave2)
+            if (row_ok && col_ok && !(fabs_(v) <= fp.t0) && !(v < mx && v > mn)) pend |= 1u << (i * NJ + j);
         }
     }
     // every lane works through its candidates one per iteration (the wave loops while any lane

@@ -68,7 +68,8 @@ __device__ __forceinline__ void descriptor_one(uint32_t e, int lane,
                                                const float4* __restrict__ feat,
                                                const int2* __restrict__ feat_info,
                                                const FeatureParams& fp,
-                                               float* __restrict__ desc, uint32_t out) {
+                                               float* __restrict__ desc, uint32_t out,
+                                               float* __restrict__ hdesc = nullptr) {
     // one wave per feature: lanes 4c..4c+3 own grid cell c (the reference's 16 threads per
     // feature, ProgramCU.cu:1017-1021); the quad evaluates consecutive window samples in
     // parallel and every lane applies the 4 contributions in the reference's (y, x) order, so
@@ -254,6 +255,8 @@ __device__ __forceinline__ void descriptor_one(uint32_t e, int lane,
         float4* dst = reinterpret_cast<float4*>(desc + (size_t)out * 128 + cell * 8 + sub * 4);
         *dst = sub == 0 ? make_float4(des[0], des[1], des[2], des[3])
                         : make_float4(des[4], des[5], des[6], des[7]);
+        if (hdesc)   // the row also to page-locked host memory (k_descriptor_wide)
+            *reinterpret_cast<float4*>(hdesc + (size_t)out * 128 + cell * 8 + sub * 4) = *dst;
     }
 }
 
@@ -839,7 +842,16 @@ static_assert(kFlatCopies >= 1 && kFlatCopies <= 32 && (kFlatCopies & (kFlatCopi
 constexpr int kFlatStride = kFlatCopies + SGK_FLAT_PAD;
 constexpr int kFlatHist = 16 * 8 * kFlatStride;
 constexpr int kFlatRows = 64;                      // window rows per chunk (one per lane)
-constexpr int kFlatWords = 2 * kFlatHist + 144;
+// + the 36-entry cell table (144 floats) + one flag word (kFlatFlag; padded to 16 bytes): set
+// when a sample of the window has a weight that is not finite.  The reference adds such a
+// weight like any other (ProgramCU.cu:1054-1082): a NaN then reaches every component through the
+// norm, and min(0.2, NaN) = 0.2 makes the row uniform; an Inf leaves 0.2 in its bins and 0
+// elsewhere (:1173-1208).  Integer sums cannot carry that: a flagged feature's row is stored as
+// NaN, and k_descriptor_nonfinite, launched after these kernels for a caller's float input
+// (FeatureParams::unit_input == 0), gives every NaN row to the exact kernel's descriptor_one.  descriptor_one
+// inside these kernels instead cost them 76-100 bytes of scratch at their 64 VGPRs.
+constexpr int kFlatFlag = 2 * kFlatHist + 144;
+constexpr int kFlatWords = kFlatFlag + 4;
 
 // A contribution as a 64-bit fixed-point word, 32 fraction bits (two's complement; |v| < 2^31):
 // the integer part by floor, the fraction (exact in float) scaled by 2^32 and truncated (error <
@@ -933,6 +945,7 @@ __device__ __forceinline__ void flat_accumulate(uint32_t e, int lane, const floa
         const float oxp = fma_(crspt, ex, srspt * ey), oyp = fma_(crspt, ey, -(srspt * ex));
         ctab[lane] = make_float4(1.0f + oxp, 1.0f - oxp, 1.0f + oyp, 1.0f - oyp);
     }
+    unsigned long long badw = 0;   // lanes that met a weight that is not finite (uniform)
     // the window's bounding rows and columns: the 5 x 5-cell square (side 5 spt, rotated) around
     // the keypoint, clamped to rows / columns 1 .. H-2 / W-2 (the reference's [1.5, W - 1.5] box)
     const float hb = 2.5f * (fabs_(cspt) + fabs_(sspt)) + 0.01f;
@@ -1022,6 +1035,10 @@ __device__ __forceinline__ void flat_accumulate(uint32_t e, int lane, const floa
             if (theta < 0) theta += 8.0f;
             const bool take = valid && ft >= 0.0f && ft <= 4.0f && fv >= 0.0f && fv <= 4.0f &&
                               theta >= 0.0f && theta < 8.0f;
+            // w >= 0 wherever it is finite; a NaN or Inf gradient makes it NaN or Inf.  Every
+            // pixel of the step counts, inside the window or not (a comparison and a scalar OR):
+            // a feature flagged for a pixel just outside its window gets the exact kernel's row.
+            badw |= __ballot(!(w < __builtin_inff()));
             if (take) {
                 const int a = (int)ft, b = (int)fv;
                 const int c00 = b * 6 + a;                 // cell (a - 1, b - 1) in the 6 x 6 table
@@ -1055,12 +1072,15 @@ __device__ __forceinline__ void flat_accumulate(uint32_t e, int lane, const floa
         }
         asm volatile("" ::: "memory");
     }
+    if (lane == 63) *reinterpret_cast<uint32_t*>(sh + kFlatFlag) = badw != 0 ? 1u : 0u;
+    asm volatile("" ::: "memory");
 }
 
 // The descriptor from nh histograms (kFlatWords floats apart from sh on): cell (ix, iy) =
 // lane >> 2, bins 2 sub, 2 sub + 1, every copy of every histogram summed as 64-bit integers --
 // the same totals however the window's pixels were split over waves and copies -- then
-// normalised (NormalizeDescriptor, ProgramCU.cu:1173-1208) and stored as row `out`.
+// normalised (NormalizeDescriptor, ProgramCU.cu:1173-1208) and stored as row `out`; a row of NaN
+// where a histogram's flag says that the window held a weight that is not finite (kFlatFlag).
 __device__ __forceinline__ void flat_finish(int lane, const FeatureParams& fp,
                                             float* __restrict__ desc, uint32_t out,
                                             const float* __restrict__ sh, int nh,
@@ -1069,6 +1089,11 @@ __device__ __forceinline__ void flat_finish(int lane, const FeatureParams& fp,
     const int ix = cell & 3, iy = cell >> 2;
     unsigned long long s0 = 0, s1 = 0;
     const int hi = ((iy * 4 + ix) * 8 + 2 * sub) * kFlatStride;
+    uint32_t nonfinite = 0;
+    for (int w = 0; w < nh; w++)
+        nonfinite |= *reinterpret_cast<const uint32_t*>(sh + w * kFlatWords + kFlatFlag);
+    // (uniform; u8, colour and -prep input is finite at every level and has no such launch)
+    const bool redo = !fp.unit_input && __builtin_amdgcn_readfirstlane(nonfinite) != 0;
     for (int w = 0; w < nh; w++) {
         const lds_u64* hc = (const lds_u64*)(sh + w * kFlatWords) + hi;
 #pragma unroll
@@ -1080,7 +1105,9 @@ __device__ __forceinline__ void flat_finish(int lane, const FeatureParams& fp,
     const double scale = 0x1p-32;
     float b0 = (float)((double)(long long)s0 * scale), b1 = (float)((double)(long long)s1 * scale);
     asm volatile("" ::: "memory");
-    if (fp.normalize) {
+    if (redo) {
+        b0 = b1 = __builtin_nanf("");
+    } else if (fp.normalize) {
         float sn = wave_sum_dpp(fma_(b0, b0, b1 * b1));
         const float n1 = __builtin_amdgcn_rsqf(sn);
         b0 = fmin_(0.2f, b0 * n1);
@@ -1192,6 +1219,29 @@ __global__ __launch_bounds__(64 * NWV) SGK_FLAT_ATTR void k_descriptor_wide(cons
     }
 }
 
+// The rows that k_descriptor_flat / _queue / _wide stored as NaN (a window sample's weight was
+// not finite, kFlatFlag) from the exact kernel's descriptor_one, which propagates NaN and Inf as
+// the reference does; launched after them.  A wave reads the first float of every 4 g-th row
+// and finds none to do on finite input.  hdesc: k_descriptor_wide's host rows (the first hcap).
+__global__ __launch_bounds__(256) void k_descriptor_nonfinite(const float* __restrict__ pyr,
+                                                              const float4* __restrict__ feat,
+                                                              const int2* __restrict__ feat_info,
+                                                              const uint32_t* __restrict__ n_feat_dev,
+                                                              const FeatureParams fp,
+                                                              float* __restrict__ desc,
+                                                              const int* __restrict__ out_index,
+                                                              float* __restrict__ hdesc, uint32_t hcap) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = *n_feat_dev;
+    for (uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {   // uniform per wave
+        const uint32_t out = out_index ? (uint32_t)out_index[e] : e;
+        const float first = desc[(size_t)out * 128];
+        if (first == first) continue;
+        descriptor_one<false>(e, lane, pyr, feat, feat_info, fp, desc, out,
+                              hdesc && out < hcap ? hdesc : nullptr);
+    }
+}
+
 // One wave per feature, grid-stride over the features (count read on the device).
 // SGK_DESC_WPE: waves per SIMD the register allocation must allow (0: the compiler's choice, 91
 // VGPRs = 5 waves; A/B knob)
@@ -1289,6 +1339,14 @@ hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* f
                  !host->hkeys || !host->hrec || !host->keys || !host->rec))
         return hipErrorInvalidValue;   // only the workgroup-per-feature kernel writes the host
     const unsigned grid = (unsigned)std::min(((long long)n_feat_cap + 3) / 4, 65536LL);
+    // after the integer-sum kernels: their NaN rows (kFlatFlag) from descriptor_one
+    auto redo_nonfinite = [&](float* hdesc, uint32_t hcap) {
+        if (hipError_t err = hipGetLastError()) return err;
+        if (fp.unit_input) return hipSuccess;   // pixels in [0, 1]: every level is finite
+        hipLaunchKernelGGL(k_descriptor_nonfinite, dim3(std::min(grid, 1024u)), dim3(256), 0, stream,
+                           pyr, feat, feat_info, n_feat_dev, fp, desc, out_index, hdesc, hcap);
+        return hipGetLastError();
+    };
     if (!exact && !rect && !dual && wide) {
         // A/B knobs: SGPU_WIDE_DESC_WAVES (4 or 8 waves per feature), SGPU_WIDE_DESC_GRID (at most
         // this many workgroups, each taking every grid-th feature)
@@ -1308,7 +1366,7 @@ hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* f
         else
             hipLaunchKernelGGL(k_descriptor_wide<4>, dim3(wgrid), dim3(256), 0, stream, pyr, feat,
                                feat_info, n_feat_dev, fp, desc, out_index, hc);
-        return hipGetLastError();
+        return redo_nonfinite(hc.hkeys ? hc.hdesc : nullptr, hc.cap);
     }
     if (!exact && !rect && !dual && queue) {
         const int nw = queue->desc_waves;
@@ -1323,12 +1381,12 @@ hipError_t launch_descriptor(const float* pyr, const float4* feat, const int2* f
         else
             hipLaunchKernelGGL(k_descriptor_queue<1>, dim3(qgrid), dim3(64), 0, stream, pyr, feat,
                                feat_info, n_feat_dev, fp, desc, out_index, qa);
-        return hipGetLastError();
+        return redo_nonfinite(nullptr, 0);
     }
     if (!exact && !rect && !dual) {
         hipLaunchKernelGGL(k_descriptor_flat, dim3(grid), dim3(256), 0, stream, pyr, feat,
                            feat_info, n_feat_dev, fp, desc, out_index);
-        return hipGetLastError();
+        return redo_nonfinite(nullptr, 0);
     }
     if (!exact && !rect) {
         hipLaunchKernelGGL(k_descriptor_dual, dim3(grid), dim3(256), 0, stream, pyr, feat,

@@ -179,6 +179,21 @@ void compute_dog(const Image& g, const Image& gp, Image* dog, std::vector<float>
 
 struct Key4 { float x, y, z, w; };
 
+// ORACLE_TIE_VARIANT (compile time; 0 = the reference's rules, what liboracle.so is built with):
+// one tie rule flipped, for tests/test_structured_images.py, which shows that the structured
+// images reach each rule (oracle/Makefile: liboracle_tie%.so).
+//   1  READ_CMP_DOG_DATA's exits take equality (v <= nmax, v >= nmin)
+//   2  the two-peak selection replaces on an equal weight (>=)
+//   3  a peak may equal the bin before it (>=)
+//   4  the one-orientation maximum moves to a later equal bin (>=)
+//   6  the first test against the row neighbours is strict (<, >)
+#ifndef ORACLE_TIE_VARIANT
+#define ORACLE_TIE_VARIANT 0
+#endif
+constexpr int kTie = ORACLE_TIE_VARIANT;
+static_assert(kTie == 0 || kTie == 1 || kTie == 2 || kTie == 3 || kTie == 4 || kTie == 6,
+              "ORACLE_TIE_VARIANT");
+
 // --- ComputeKEY_Kernel (ProgramCU.cu:553-671) with READ_CMP_DOG_DATA (:534-550).
 //     Interior pixels only (row, col in [1, dim-2]); the comparison order and the early exits
 //     are kept, because ties are resolved by that order.
@@ -202,12 +217,12 @@ void compute_key(const Image& dp, const Image& dc, const Image& dn, float t0, fl
                     nmax = fmax_(nmax, d3[0]);
                     nmax = fmax_(nmax, d3[1]);
                     nmax = fmax_(nmax, d3[2]);
-                    if (v < nmax) return false;
+                    if (kTie == 1 ? v <= nmax : v < nmax) return false;
                 } else {
                     nmin = fmin_(nmin, d3[0]);
                     nmin = fmin_(nmin, d3[1]);
                     nmin = fmin_(nmin, d3[2]);
-                    if (v > nmin) return false;
+                    if (kTie == 1 ? v >= nmin : v > nmin) return false;
                 }
                 return true;
             };
@@ -217,7 +232,7 @@ void compute_key(const Image& dp, const Image& dc, const Image& dn, float t0, fl
             data[1][2] = dc.px[idx[1] + 1];
             nmax = fmax_(data[1][0], data[1][2]);
             nmin = fmin_(data[1][0], data[1][2]);
-            if (v <= nmax && v >= nmin) goto finish;
+            if (kTie == 6 ? (v < nmax && v > nmin) : (v <= nmax && v >= nmin)) goto finish;
             if (!read_cmp(data[0], dc, idx[0])) goto finish;
             if (!read_cmp(data[2], dc, idx[2])) goto finish;
             {
@@ -443,7 +458,7 @@ void orientation_key(Key4 key, const std::vector<float>& grad, int W, int H,
         int index_max = 0;
         float max_vote = vote[0];
         for (int i = 1; i < 36; ++i) {
-            index_max = vote[i] > max_vote ? i : index_max;
+            index_max = (kTie == 4 ? vote[i] >= max_vote : vote[i] > max_vote) ? i : index_max;
             max_vote = fmax_(max_vote, vote[i]);
         }
         float pre = vote[index_max == 0 ? 35 : index_max - 1];
@@ -462,12 +477,13 @@ void orientation_key(Key4 key, const std::vector<float>& grad, int W, int H,
     int ocount = 0;
     for (int i = 0; i < 36; ++i) {
         float next = vote[i + 1];
-        if (vote[i] > vote_threshold && vote[i] > pre && vote[i] > next) {
+        if (vote[i] > vote_threshold && (kTie == 3 ? vote[i] >= pre : vote[i] > pre) &&
+            vote[i] > next) {
             float di = 0.5f * fdiv(next - pre, vote[i] + vote[i] - next - pre);
             float rot = i + di + 0.5f;
             float weight = vote[i];
-            if (weight > max_vot[1]) {
-                if (weight > max_vot[0]) {
+            if (kTie == 2 ? weight >= max_vot[1] : weight > max_vot[1]) {
+                if (kTie == 2 ? weight >= max_vot[0] : weight > max_vot[0]) {
                     max_vot[1] = max_vot[0];
                     max_rot[1] = max_rot[0];
                     max_vot[0] = weight;
@@ -1209,12 +1225,12 @@ int oracle_extract_f32(const float* img, int w, int h, int stride, const sgpu_op
     }
 }
 
-int oracle_gaussian(const uint8_t* img, int w, int h, int stride, const sgpu_options* opt,
-                    int octave, int level, float* out, int cap) {
+static int gaussian_of(const uint8_t* img, const float* img_f32, int w, int h, int stride,
+                       const sgpu_options* opt, int octave, int level, float* out, int cap) {
     try {
         sgpu_options o2 = *opt;
         o2.descriptors = 0;
-        oracle::Result R = oracle::extract(img, w, h, stride, o2, true);
+        oracle::Result R = oracle::extract(img, w, h, stride, o2, true, img_f32);
         if (octave >= (int)R.gauss.size()) return -1;
         const oracle::Image& g = R.gauss[octave][level];
         if ((int)g.px.size() > cap) return -4;
@@ -1225,13 +1241,24 @@ int oracle_gaussian(const uint8_t* img, int w, int h, int stride, const sgpu_opt
     }
 }
 
+int oracle_gaussian(const uint8_t* img, int w, int h, int stride, const sgpu_options* opt,
+                    int octave, int level, float* out, int cap) {
+    return gaussian_of(img, nullptr, w, h, stride, opt, octave, level, out, cap);
+}
+
+// The same for float luminance input (oracle_extract_f32's pyramid).
+int oracle_gaussian_f32(const float* img, int w, int h, int stride, const sgpu_options* opt,
+                        int octave, int level, float* out, int cap) {
+    return gaussian_of(nullptr, img, w, h, stride, opt, octave, level, out, cap);
+}
+
 // Candidates in reference order: ints {col,row,level_id,0}, floats {dx,dy,ds,0}.
-int oracle_candidates(const uint8_t* img, int w, int h, int stride, const sgpu_options* opt,
-                      int* ints, float* floats, int cap, int* n_out) {
+static int candidates_of(const uint8_t* img, const float* img_f32, int w, int h, int stride,
+                         const sgpu_options* opt, int* ints, float* floats, int cap, int* n_out) {
     try {
         sgpu_options o2 = *opt;
         o2.descriptors = 0;
-        oracle::Result R = oracle::extract(img, w, h, stride, o2, false);
+        oracle::Result R = oracle::extract(img, w, h, stride, o2, false, img_f32);
         int n = 0, d = opt->dog_level_num;
         for (const auto& L : R.levels)
             for (const auto& c : L.candidates) {
@@ -1248,6 +1275,16 @@ int oracle_candidates(const uint8_t* img, int w, int h, int stride, const sgpu_o
     } catch (const std::invalid_argument&) {
         return -2;   // options the reference cannot run (see oracle::extract)
     }
+}
+
+int oracle_candidates(const uint8_t* img, int w, int h, int stride, const sgpu_options* opt,
+                      int* ints, float* floats, int cap, int* n_out) {
+    return candidates_of(img, nullptr, w, h, stride, opt, ints, floats, cap, n_out);
+}
+
+int oracle_candidates_f32(const float* img, int w, int h, int stride, const sgpu_options* opt,
+                          int* ints, float* floats, int cap, int* n_out) {
+    return candidates_of(nullptr, img, w, h, stride, opt, ints, floats, cap, n_out);
 }
 
 // Features in octave coordinates (x, y, s, o: the descriptor's input) with their level id

@@ -62,6 +62,8 @@ def lib():
         L.oracle_guided_pass.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_float] * 6
         L.oracle_first_octave_input.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [
             ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        for f in (L.oracle_gaussian_f32, L.oracle_candidates_f32):
+            f.argtypes = getattr(L, f.__name__[:-4]).argtypes
         L.oracle_extract_f32.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int, ctypes.c_void_p]
@@ -98,6 +100,11 @@ def lib():
 def _img(img):
     img = np.ascontiguousarray(img, dtype=np.uint8)
     return img, img.ctypes.data
+
+
+def _is_f32(img):
+    """Float luminance input (extract_f32's ingest) rather than u8."""
+    return np.asarray(img).dtype == np.float32
 
 
 def extract(img: np.ndarray, opts: SgpuOptions | None = None):
@@ -143,26 +150,35 @@ def gray_from_color(img: np.ndarray, fmt: str) -> np.ndarray:
 
 
 def gaussian(img, octave, level, opts=None):
+    """Level `level` of octave `octave`; img u8, or float32 for the float luminance input."""
     opts = opts or default_options()
-    img, p = _img(img)
+    if _is_f32(img):
+        img, fn = np.ascontiguousarray(img), lib().oracle_gaussian_f32
+        p = img.ctypes.data
+    else:
+        (img, p), fn = _img(img), lib().oracle_gaussian
     h, w = img.shape
     cap = (w + 4) * h * (1 << (2 * max(0, -opts.octave_min)))
     out = np.zeros(cap, np.float32)
-    n = lib().oracle_gaussian(p, w, h, w, ctypes.byref(opts), octave, level, out.ctypes.data, cap)
+    n = fn(p, w, h, w, ctypes.byref(opts), octave, level, out.ctypes.data, cap)
     assert n > 0, n
     return out[:n]
 
 
 def candidates(img, opts=None):
+    """(ints [n,4] col, row, level id, 0; floats [n,4] dx, dy, ds, 0); img u8 or float32."""
     opts = opts or default_options()
-    img, p = _img(img)
+    if _is_f32(img):
+        img, fn = np.ascontiguousarray(img), lib().oracle_candidates_f32
+        p = img.ctypes.data
+    else:
+        (img, p), fn = _img(img), lib().oracle_candidates
     h, w = img.shape
     n = ctypes.c_int(0)
-    lib().oracle_candidates(p, w, h, w, ctypes.byref(opts), None, None, 0, ctypes.byref(n))
+    fn(p, w, h, w, ctypes.byref(opts), None, None, 0, ctypes.byref(n))
     ints = np.zeros((max(n.value, 1), 4), np.int32)
     fl = np.zeros((max(n.value, 1), 4), np.float32)
-    lib().oracle_candidates(p, w, h, w, ctypes.byref(opts), ints.ctypes.data, fl.ctypes.data,
-                            n.value, ctypes.byref(n))
+    fn(p, w, h, w, ctypes.byref(opts), ints.ctypes.data, fl.ctypes.data, n.value, ctypes.byref(n))
     return ints[:n.value], fl[:n.value]
 
 

@@ -12,18 +12,27 @@ import pytest
 
 import oracle_py as O
 import ref_numpy as R
+import structured_images as SI
 from sgpu_types import default_options
 from sift_synth import synth_image
 
-# (name, width, height, seed, oracle option overrides): the default case; config C2's 1080p
+# (name, image, oracle option overrides, candidates): the default case; config C2's 1080p
 # image; the circular orientation window (ProgramCU-0.cu:834); -fo -1 (the upsampled first
-# octave); -d 5 (other level sigmas and filter widths)
+# octave); -d 5 (other level sigmas and filter widths); then the tie-free structured images
+# (tests/structured_images.py: binary edges, plateaus at 0 and 255), whose candidate counts are
+# the oracle's, stated exactly (binary_disks has 100, not more than the floor of 100 that keeps
+# the noise cases from being empty).  The structured images with ties are left out on purpose:
+# there float32 rounding and the tie order decide the candidate set (Jaccard 0.106 with
+# float64 on checker8), which is what the GPU has to reproduce, not float64.
 CASES = [
-    ("default", 320, 240, 21, {}),
-    ("c2_1080p", 1920, 1080, 2000, {"octave_num": 4}),
-    ("circular", 320, 240, 22, {"circular_window": 1}),
-    ("fo_m1", 320, 240, 23, {"octave_min": -1, "octave_num": 4}),
-    ("d5", 320, 240, 24, {"dog_level_num": 5}),
+    ("default", lambda: synth_image(320, 240, 21), {}, None),
+    ("c2_1080p", lambda: synth_image(1920, 1080, 2000), {"octave_num": 4}, None),
+    ("circular", lambda: synth_image(320, 240, 22), {"circular_window": 1}, None),
+    ("fo_m1", lambda: synth_image(320, 240, 23), {"octave_min": -1, "octave_num": 4}, None),
+    ("d5", lambda: synth_image(320, 240, 24), {"dog_level_num": 5}, None),
+    ("binary_blocks4", SI.binary_blocks4, {}, 795),
+    ("binary_disks", SI.binary_disks, {}, 100),
+    ("saturated_sines", SI.saturated_sines, {}, 200),
 ]
 # at most this many features per case go through the per-feature float64 loops
 MAX_FEATS = 400
@@ -31,12 +40,12 @@ MAX_FEATS = 400
 
 @pytest.fixture(scope="module", params=CASES, ids=[c[0] for c in CASES])
 def case(request):
-    name, w, h, seed, over = request.param
-    img = synth_image(w, h, seed)
+    name, image, over, count = request.param
+    img = image()
     opts = default_options(**over)
     S = R.schedule(d=opts.dog_level_num, octave_min=opts.octave_min)
     G = R.pyramid(img, S, octave_num=opts.octave_num, octave_min=opts.octave_min)
-    return img, S, G, opts
+    return img, S, G, opts, count
 
 
 def _sample(n):
@@ -45,15 +54,18 @@ def _sample(n):
 
 
 def test_pyramid_levels(case):
-    img, S, G, opts = case
+    img, S, G, opts, count = case
+    worst = 0.0
     for o, lv in enumerate(G):
         for k, g64 in enumerate(lv):
             g32 = O.gaussian(img, o, k, opts).reshape(g64.shape)
-            assert np.max(np.abs(g32 - g64)) < 2e-5, (o, k)
+            worst = max(worst, np.max(np.abs(g32 - g64)))
+            assert worst < 2e-5, (o, k)
+    print(f"levels: max |float32 - float64| {worst:.3g}")
 
 
 def test_candidates(case):
-    img, S, G, opts = case
+    img, S, G, opts, count = case
     cand64 = R.detect(G, S)
     ints, fl = O.candidates(img, opts)
     d = S["d"]
@@ -66,7 +78,8 @@ def test_candidates(case):
             ref[(o, j, c, r)] = np.array([dx, dy, ds])
     common = sorted(set(ours) & set(ref))
     union = set(ours) | set(ref)
-    assert len(ours) > 100
+    assert len(ours) > 100 if count is None else len(ours) == count
+    print(f"candidates {len(ours)}, float64 {len(ref)}, common {len(common)}")
     assert len(common) / len(union) > 0.97, (len(ours), len(ref), len(common))
     # The 3x3 solve (ProgramCU.cu:631-667) amplifies the oracle's float32 rounding of the
     # Gaussian levels by |A^-1| where the curvature is small, so the offsets are held to a
@@ -99,7 +112,7 @@ def _solve_unit(G, S, key):
 
 
 def test_orientations(case):
-    img, S, G, opts = case
+    img, S, G, opts, count = case
     feat, lvl = O.features_oct(img, opts)
     d = S["d"]
     grads = {}
@@ -120,7 +133,7 @@ def test_orientations(case):
 
 
 def test_descriptors(case):
-    img, S, G, opts = case
+    img, S, G, opts, count = case
     feat, lvl = O.features_oct(img, opts)
     _, desc = O.extract(img, opts)
     d = S["d"]
@@ -141,7 +154,7 @@ def test_descriptors(case):
 
 
 def test_unnormalized_descriptors(case):
-    img, S, G, opts = case
+    img, S, G, opts, count = case
     opts = default_options(**{f: getattr(opts, f) for f, _ in opts._fields_})
     opts.normalized = 0
     feat, lvl = O.features_oct(img, opts)
