@@ -325,7 +325,8 @@ int sgpu_match_images_guided(sgpu_ctx* ctx, const int* image_pairs, int npairs,
  *  - a pair with fewer matches than the minimal sample, or without a valid hypothesis, has no
  *    model: zeros, 0 inliers, a zero mask; fed to a guided call it yields no matches;
  *  - F is the minimal-sample solution WITHOUT rank-2 enforcement (the Sampson test does not need
- *    it; a caller that wants epipoles enforces rank 2 itself).  No local refinement.
+ *    it; a caller that wants epipoles enforces rank 2 itself).  No local refinement: the
+ *    _refined forms below add it.
  * The number of launches, copies and synchronisations does not depend on npairs;
  * sgpu_last_timing's times[12] is the call's device time.
  * SGPU_EINVAL: a pair index outside [0, nsets), decreasing offsets, a negative count, a match
@@ -348,6 +349,36 @@ int sgpu_estimate_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
                          const int* matches, const int* match_counts,
                          int model, float threshold, int iterations, uint32_t seed,
                          float* out_models, int* out_inliers, uint8_t* out_mask);
+/* The estimator followed by local refinement, still one call on the device: the winner of every
+ * pair is refitted by least squares on its own inliers, up to refine_rounds times (0 .. 16;
+ * outside: SGPU_EINVAL; 0 returns the bits of the unrefined call).  One round (csrc/sift_geom.h
+ * defines the arithmetic):
+ *  - both images' inlier points are normalised (centroid to the origin, mean absolute deviation
+ *    per coordinate to 1), the 9 x 9 normal matrix of the DLT rows (H: two per inlier) or of the
+ *    eight-point rows (F) is summed in double, and the eigenvector of its smallest eigenvalue,
+ *    by cyclic Jacobi, is denormalised, scaled to unit Frobenius norm and rounded to float.  F
+ *    stays without rank-2 enforcement; there is no sign convention;
+ *  - the refit is scored with the same inlier test over all matches of the pair.  Fewer inliers
+ *    than before: the round is rejected and the loop ends with the model it had.  Otherwise the
+ *    refit, its mask and its count replace the model's, and the loop ends early when the mask
+ *    did not change (the next refit would be the same) or a refit is degenerate.
+ * So out_inliers[p] is never below the unrefined call's, out_mask is still exactly the guided test
+ * of out_models[p], a pair without a model stays without one, and the result is a pure function of
+ * the inputs and the seed.  out_rounds (or NULL) [npairs] = the accepted rounds of every pair.  The
+ * launches, copies and synchronisations depend neither on npairs nor on refine_rounds (one more
+ * launch than the unrefined call, none more for 0); times[12] covers it.  All other arguments,
+ * flags, outputs and error conditions are those of sgpu_estimate_batch / sgpu_estimate_images. */
+int sgpu_estimate_batch_refined(sgpu_ctx* ctx, const float* loc, const int64_t* set_offsets,
+                                int nsets, const int* set_pairs, int npairs, const int* matches,
+                                const int* match_counts, int model, float threshold,
+                                int iterations, uint32_t seed, int refine_rounds,
+                                float* out_models, int* out_inliers, uint8_t* out_mask,
+                                int* out_rounds /* [npairs] or NULL */, int flags);
+int sgpu_estimate_images_refined(sgpu_ctx* ctx, const int* image_pairs, int npairs,
+                                 const int* matches, const int* match_counts,
+                                 int model, float threshold, int iterations, uint32_t seed,
+                                 int refine_rounds, float* out_models, int* out_inliers,
+                                 uint8_t* out_mask, int* out_rounds /* [npairs] or NULL */);
 
 /* Timing of the last call: stage times in milliseconds measured with HIP events
  * (SiftGPU::_timing, SiftPyramid.cpp:48-56).  times[0..7] =

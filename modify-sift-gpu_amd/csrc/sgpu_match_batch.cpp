@@ -255,12 +255,13 @@ int sgpu_match_images_guided(sgpu_ctx* ctx, const int* image_pairs, int npairs, 
 // loc: device locations (x, y of buffer row r at loc[r * stride]), or host_loc: packed host
 // locations uploaded here, after every argument has been checked.  One table upload
 // ([pairs][items][matches]), one memset, three launches, two device->host copies and one
-// synchronisation, whatever npairs is.
+// synchronisation, whatever npairs is.  rounds > 0 (the _refined calls): one more launch, the
+// local refinement of every pair's winner, and its accepted rounds in the same result copy.
 static int estimate_impl(sgpu_ctx* ctx, const float* loc, int stride, const float* host_loc,
                          const int64_t* off, int nsets, const int* set_pairs, int npairs,
                          const int* matches, const int* counts, int model, float threshold,
                          int iterations, uint32_t seed, float* out_models, int* out_inliers,
-                         uint8_t* out_mask) {
+                         uint8_t* out_mask, int rounds, int* out_rounds) {
     hipStream_t st = ctx->stream;
     sgeo::Plan& plan = ctx->e_hplan;
     const int prc = sgeo::build_plan(off, nsets, set_pairs, npairs, counts, model, iterations, plan);
@@ -291,9 +292,10 @@ static int estimate_impl(sgpu_ctx* ctx, const float* loc, int stride, const floa
     memcpy(tb, plan.pairs.data(), b_pairs);
     if (b_items) memcpy(tb + b_pairs, plan.items.data(), b_items);
     if (b_matches) memcpy(tb + b_pairs + b_items, matches, b_matches);
-    // [models npairs x 9 floats][inliers npairs][error flag]
+    // [models npairs x 9 floats][inliers npairs][error flag][accepted rounds npairs, if refined]
     const size_t b_models = (size_t)npairs * 9 * sizeof(float);
-    const size_t b_result = b_models + (size_t)(npairs + 1) * sizeof(int);
+    const size_t b_plain = b_models + (size_t)(npairs + 1) * sizeof(int);
+    const size_t b_result = b_plain + (rounds > 0 ? (size_t)npairs * sizeof(int) : 0);
     const size_t b_slots = (size_t)npairs * sizeof(unsigned long long);
     ALLOCCHK(ctx, ctx->e_plan.ensure(ctx->e_tables.size()));
     ALLOCCHK(ctx, ctx->e_pts.ensure((size_t)std::max<long long>(total, 1) * sizeof(float4)));
@@ -310,6 +312,7 @@ static int estimate_impl(sgpu_ctx* ctx, const float* loc, int stride, const floa
     float* d_models = ctx->e_out.as<float>();
     int* d_inliers = reinterpret_cast<int*>(ctx->e_out.as<unsigned char>() + b_models);
     int* d_err = d_inliers + npairs;
+    int* d_rounds = d_err + 1;
     float4* d_pts = ctx->e_pts.as<float4>();
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
     HIPCHK(ctx, hipMemsetAsync(d_slots, 0, b_slots, st));
@@ -320,6 +323,9 @@ static int estimate_impl(sgpu_ctx* ctx, const float* loc, int stride, const floa
     HIPCHK(ctx, sgk::launch_estimate_finish(d_pts, d_pairs, npairs, model, threshold, seed, d_slots,
                                             d_models, d_inliers,
                                             out_mask ? ctx->e_mask.as<uint8_t>() : nullptr, d_err, st));
+    HIPCHK(ctx, sgk::launch_estimate_refine(d_pts, d_pairs, npairs, model, threshold, rounds, d_models,
+                                            d_inliers, out_mask ? ctx->e_mask.as<uint8_t>() : nullptr,
+                                            d_rounds, st));
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->e_result.data(), ctx->e_out.p, b_result, hipMemcpyDeviceToHost, st));
     if (out_mask && total > 0)
@@ -328,31 +334,41 @@ static int estimate_impl(sgpu_ctx* ctx, const float* loc, int stride, const floa
     (void)hipEventElapsedTime(&ctx->timing[T_ESTIMATE], ctx->ev[1], ctx->ev[2]);
     memcpy(out_models, ctx->e_result.data(), b_models);
     memcpy(out_inliers, ctx->e_result.data() + b_models, (size_t)npairs * sizeof(int));
+    if (out_rounds) {
+        if (rounds > 0) memcpy(out_rounds, ctx->e_result.data() + b_plain, (size_t)npairs * sizeof(int));
+        else memset(out_rounds, 0, (size_t)npairs * sizeof(int));
+    }
     int err = 0;
     memcpy(&err, ctx->e_result.data() + b_models + (size_t)npairs * sizeof(int), sizeof(int));
     if (err) return ctx->fail(SGPU_ENODEV, "estimate: a regenerated winner's inlier count differs from its score");
     return SGPU_OK;
 }
 
-int sgpu_estimate_batch(sgpu_ctx* ctx, const float* loc, const int64_t* set_offsets, int nsets,
-                        const int* set_pairs, int npairs, const int* matches,
-                        const int* match_counts, int model, float threshold, int iterations,
-                        uint32_t seed, float* out_models, int* out_inliers, uint8_t* out_mask,
-                        int flags) {
+int sgpu_estimate_batch_refined(sgpu_ctx* ctx, const float* loc, const int64_t* set_offsets,
+                                int nsets, const int* set_pairs, int npairs, const int* matches,
+                                const int* match_counts, int model, float threshold,
+                                int iterations, uint32_t seed, int refine_rounds, float* out_models,
+                                int* out_inliers, uint8_t* out_mask, int* out_rounds, int flags) {
     if (!ctx) return SGPU_EINVAL;
     if (nsets < 0 || npairs < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad estimate batch arguments");
+    if (refine_rounds < 0 || refine_rounds > sgeo::kMaxRefineRounds)
+        return ctx->fail(SGPU_EINVAL, "refine_rounds outside [0, 16]");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool dev = (flags & SGPU_INPUT_DEVICE) != 0;
     return estimate_impl(ctx, dev ? loc : nullptr, 2, dev ? nullptr : loc, set_offsets, nsets,
                          set_pairs, npairs, matches, match_counts, model, threshold, iterations, seed,
-                         out_models, out_inliers, out_mask);
+                         out_models, out_inliers, out_mask, refine_rounds, out_rounds);
 }
 
-int sgpu_estimate_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, const int* matches,
-                         const int* match_counts, int model, float threshold, int iterations,
-                         uint32_t seed, float* out_models, int* out_inliers, uint8_t* out_mask) {
+int sgpu_estimate_images_refined(sgpu_ctx* ctx, const int* image_pairs, int npairs,
+                                 const int* matches, const int* match_counts, int model,
+                                 float threshold, int iterations, uint32_t seed, int refine_rounds,
+                                 float* out_models, int* out_inliers, uint8_t* out_mask,
+                                 int* out_rounds) {
     if (!ctx) return SGPU_EINVAL;
     if (npairs < 0) return ctx->fail(SGPU_EINVAL, "bad estimate arguments");
+    if (refine_rounds < 0 || refine_rounds > sgeo::kMaxRefineRounds)
+        return ctx->fail(SGPU_EINVAL, "refine_rounds outside [0, 16]");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // the states sgpu_match_images_guided refuses (feature_u8), without its quantisation
     if (ctx->batch <= 0 || ctx->img_off.empty())
@@ -363,7 +379,26 @@ int sgpu_estimate_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, cons
     if (rc != SGPU_OK) return rc;
     return estimate_impl(ctx, keys, 4, nullptr, ctx->img_off.data(), ctx->batch, image_pairs, npairs,
                          matches, match_counts, model, threshold, iterations, seed, out_models,
-                         out_inliers, out_mask);
+                         out_inliers, out_mask, refine_rounds, out_rounds);
+}
+
+// the unrefined forms: no round, no launch added
+int sgpu_estimate_batch(sgpu_ctx* ctx, const float* loc, const int64_t* set_offsets, int nsets,
+                        const int* set_pairs, int npairs, const int* matches,
+                        const int* match_counts, int model, float threshold, int iterations,
+                        uint32_t seed, float* out_models, int* out_inliers, uint8_t* out_mask,
+                        int flags) {
+    return sgpu_estimate_batch_refined(ctx, loc, set_offsets, nsets, set_pairs, npairs, matches,
+                                       match_counts, model, threshold, iterations, seed, 0, out_models,
+                                       out_inliers, out_mask, nullptr, flags);
+}
+
+int sgpu_estimate_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, const int* matches,
+                         const int* match_counts, int model, float threshold, int iterations,
+                         uint32_t seed, float* out_models, int* out_inliers, uint8_t* out_mask) {
+    return sgpu_estimate_images_refined(ctx, image_pairs, npairs, matches, match_counts, model,
+                                        threshold, iterations, seed, 0, out_models, out_inliers,
+                                        out_mask, nullptr);
 }
 
 }  // extern "C"

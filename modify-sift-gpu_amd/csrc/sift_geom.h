@@ -11,6 +11,8 @@
 //   score    the guided matcher's own test in float (inlier()), counted over all m matches;
 //   winner   the most inliers, then the lowest t; a pair with m < S or no valid hypothesis has no
 //            model: zeros, 0 inliers, a zero mask.
+//   refine   (sgpu_estimate_*_refined only) up to `rounds` least-squares refits of the winner on
+//            its inliers, each accepted only when it loses no inlier: "local refinement" below.
 // F is the minimal-sample solution WITHOUT rank-2 enforcement: the Sampson test does not need it; a
 // caller that wants epipoles enforces rank 2 itself.
 //
@@ -20,6 +22,7 @@
 // compile-time indices only: a runtime-indexed per-lane array would live in scratch memory.
 #ifndef SIFT_GEOM_H
 #define SIFT_GEOM_H
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -403,6 +406,340 @@ inline void estimate_host(const float* loc, int loc_stride, const int64_t* set_o
             n += in;
         }
         out_inliers[p] = n;
+        moff += m;
+    }
+}
+
+// ---- local refinement ----------------------------------------------------------------------------
+//
+// Contract.  The winner gives M, its mask and its count c.  Round r = 1 .. rounds:
+//   1  stop when c < S;
+//   2  refit<MODEL> over the inliers of M: a double[9] at unit Frobenius norm; invalid -> stop;
+//   3  round to float: M'; score M' with inlier() over all m matches: mask', c';
+//   4  c' < c: reject, keep M, stop;
+//   5  accept M', mask', c'; mask' equal to the mask before: stop (the next refit would give M').
+// So the count never falls, and the mask stays the guided test of the returned float matrix.
+//
+// refit: both images' inlier points normalised as normalise8 does (centroid to the origin, mean
+// absolute deviation per coordinate to 1, an IEEE division by the inlier count), the 9 x 9 normal
+// matrix N = sum a a' of the rows a (F: solve_f's row; H: the two DLT rows of the normalised
+// correspondence), the eigenvector of N's smallest eigenvalue by cyclic Jacobi, denormalised
+// (H: inv(T2) G T1; F: T2' G T1) and scaled by unit_norm.  No sign convention, no rank-2 step.
+// Invalid: fewer than S inliers, a mean deviation <= kPivotEps, or unit_norm fails.
+//
+// Summation order: every sum over the inliers is kRefineLanes partial sums, partial l over the
+// inlier matches k = l (mod 64) in ascending k, then part[l] += part[l + stride] for l < stride,
+// stride = 32, 16 .. 1 (fold_lanes; a xor butterfly over a wave's lanes associates the same way).
+// Jacobi: rotations (p, q), p < q in row order, kJacobiSweeps sweeps, a rotation skipped when the
+// off-diagonal entry is exactly 0; row k of A and V is one lane's work on the device (k_estimate_
+// refine keeps both in LDS), and the element arithmetic below is shared, so the bits are too.
+
+constexpr int kRefineLanes = 64;
+constexpr int kMaxRefineRounds = 16;
+constexpr int kNormalEntries = 45;   // the upper triangle of N, row-major
+// The measured maximum plus two.  Sweeps until the off-diagonal Frobenius norm is <= 1e-14 of the
+// matrix's: at most 6 over the refit matrices of the test scenes, at most 7 over 1,000 random PSD
+// 9 x 9 matrices (tests/abi/geom_refine_check.cpp measures; tests/test_geom_refine.py fails when
+// the maximum + 2 differs from this).
+constexpr int kJacobiSweeps = 9;
+
+enum { kStopBudget = 0, kStopFixedPoint = 1, kStopRejected = 2, kStopInvalid = 3, kStopNoModel = 4 };
+
+// the normalisation of the two images: centroids, mean deviations d and their inverses s
+struct RefitNorm {
+    double c1x, c1y, c2x, c2y;
+    double d1, s1, d2, s2;
+};
+// sum[4] = the sums of x1, y1, x2, y2 over n inliers
+SGEO_HD void refit_centroids(const double* sum, int n, RefitNorm& nm) {
+    const double dn = (double)n;
+    nm.c1x = sum[0] / dn;
+    nm.c1y = sum[1] / dn;
+    nm.c2x = sum[2] / dn;
+    nm.c2y = sum[3] / dn;
+}
+// one inlier's terms of the two deviation sums
+SGEO_HD void refit_deviation(const RefitNorm& nm, double x1, double y1, double x2, double y2,
+                             double& t1, double& t2) {
+    t1 = __builtin_fabs(x1 - nm.c1x) + __builtin_fabs(y1 - nm.c1y);
+    t2 = __builtin_fabs(x2 - nm.c2x) + __builtin_fabs(y2 - nm.c2y);
+}
+SGEO_HD bool refit_scales(double dev1, double dev2, int n, RefitNorm& nm) {
+    const double dn = 2.0 * (double)n;
+    nm.d1 = dev1 / dn;
+    nm.d2 = dev2 / dn;
+    if (!((nm.d1 > kPivotEps) & (nm.d2 > kPivotEps))) return false;
+    nm.s1 = 1.0 / nm.d1;
+    nm.s2 = 1.0 / nm.d2;
+    return true;
+}
+// N (45 entries, the upper triangle in row-major order) += a a' of one inlier's row(s)
+SGEO_HD void normal_add(const double* a, double* N) {
+    int e = 0;
+    SGEO_UNROLL
+    for (int i = 0; i < 9; i++) {
+        SGEO_UNROLL
+        for (int j = i; j < 9; j++) {
+            N[e] = __builtin_fma(a[i], a[j], N[e]);
+            e++;
+        }
+    }
+}
+template <int MODEL>
+SGEO_HD void refit_accumulate(const RefitNorm& nm, double x1, double y1, double x2, double y2,
+                              double* N) {
+    const double u1 = (x1 - nm.c1x) * nm.s1, v1 = (y1 - nm.c1y) * nm.s1;
+    const double u2 = (x2 - nm.c2x) * nm.s2, v2 = (y2 - nm.c2y) * nm.s2;
+    if (MODEL == kModelF) {
+        const double a[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1.0};
+        normal_add(a, N);
+    } else {
+        // h . a = 0, h . b = 0 for (u2, v2, 1) x (H (u1, v1, 1)) = 0
+        const double a[9] = {0.0, 0.0, 0.0, -u1, -v1, -1.0, v2 * u1, v2 * v1, v2};
+        const double b[9] = {u1, v1, 1.0, 0.0, 0.0, 0.0, -(u2 * u1), -(u2 * v1), -u2};
+        normal_add(a, N);
+        normal_add(b, N);
+    }
+}
+// the eigenvector g (normalised coordinates) back to pixels, at unit Frobenius norm
+template <int MODEL>
+SGEO_HD bool refit_denormalise(const RefitNorm& nm, const double* g, double* out) {
+    double r[9];   // G T1, T = [s 0 -s cx; 0 s -s cy; 0 0 1]
+    SGEO_UNROLL
+    for (int i = 0; i < 3; i++) {
+        r[3 * i] = g[3 * i] * nm.s1;
+        r[3 * i + 1] = g[3 * i + 1] * nm.s1;
+        r[3 * i + 2] = g[3 * i + 2] - __builtin_fma(r[3 * i], nm.c1x, r[3 * i + 1] * nm.c1y);
+    }
+    double M[9];
+    SGEO_UNROLL
+    for (int c = 0; c < 3; c++) {
+        if (MODEL == kModelF) {   // T2' R
+            M[c] = r[c] * nm.s2;
+            M[3 + c] = r[3 + c] * nm.s2;
+            M[6 + c] = r[6 + c] - __builtin_fma(M[c], nm.c2x, M[3 + c] * nm.c2y);
+        } else {                  // inv(T2) R, inv(T) = [d 0 cx; 0 d cy; 0 0 1]
+            M[c] = __builtin_fma(r[c], nm.d2, nm.c2x * r[6 + c]);
+            M[3 + c] = __builtin_fma(r[3 + c], nm.d2, nm.c2y * r[6 + c]);
+            M[6 + c] = r[6 + c];
+        }
+    }
+    return unit_norm(M, out);
+}
+
+// The Jacobi rotation that annihilates a_pq (a_pq != 0): t = tan, c = cos, s = sin of the angle.
+struct JacobiRot { double t, c, s; };
+SGEO_HD JacobiRot jacobi_rotation(double app, double aqq, double apq) {
+    const double tau = (aqq - app) / (2.0 * apq);
+    const double root = __builtin_sqrt(__builtin_fma(tau, tau, 1.0));
+    JacobiRot r;
+    r.t = (tau >= 0.0 ? 1.0 : -1.0) / (__builtin_fabs(tau) + root);
+    r.c = 1.0 / __builtin_sqrt(__builtin_fma(r.t, r.t, 1.0));
+    r.s = r.t * r.c;
+    return r;
+}
+// columns p, q of one row (of A off the 2 x 2 block, or of V): (x, y) -> (c x - s y, s x + c y)
+SGEO_HD void jacobi_apply(const JacobiRot& r, double x, double y, double& xo, double& yo) {
+    xo = __builtin_fma(r.c, x, -(r.s * y));
+    yo = __builtin_fma(r.s, x, r.c * y);
+}
+SGEO_HD double jacobi_app(const JacobiRot& r, double app, double apq) { return __builtin_fma(-r.t, apq, app); }
+SGEO_HD double jacobi_aqq(const JacobiRot& r, double aqq, double apq) { return __builtin_fma(r.t, apq, aqq); }
+
+// one sweep over A (symmetric, 9 x 9, both triangles stored) and V, in place
+inline void jacobi_sweep_host(double* A, double* V) {
+    for (int p = 0; p < 8; p++) {
+        for (int q = p + 1; q < 9; q++) {
+            const double app = A[9 * p + p], aqq = A[9 * q + q], apq = A[9 * p + q];
+            if (apq == 0.0) continue;
+            const JacobiRot r = jacobi_rotation(app, aqq, apq);
+            for (int k = 0; k < 9; k++) {
+                jacobi_apply(r, V[9 * k + p], V[9 * k + q], V[9 * k + p], V[9 * k + q]);
+                if (k == p) {
+                    A[9 * p + p] = jacobi_app(r, app, apq);
+                    A[9 * p + q] = 0.0;
+                } else if (k == q) {
+                    A[9 * q + q] = jacobi_aqq(r, aqq, apq);
+                    A[9 * q + p] = 0.0;
+                } else {
+                    double x, y;
+                    jacobi_apply(r, A[9 * k + p], A[9 * k + q], x, y);
+                    A[9 * k + p] = A[9 * p + k] = x;
+                    A[9 * k + q] = A[9 * q + k] = y;
+                }
+            }
+        }
+    }
+}
+// the index of the smallest diagonal entry, the lowest among equal ones
+SGEO_HD int jacobi_min_index(const double* A) {
+    int best = 0;
+    double v = A[0];
+    SGEO_UNROLL
+    for (int i = 1; i < 9; i++) {
+        const double d = A[10 * i];
+        const bool lt = d < v;
+        v = lt ? d : v;
+        best = lt ? i : best;
+    }
+    return best;
+}
+// N (45) -> A (81, both triangles), V = I
+inline void jacobi_start_host(const double* N, double* A, double* V) {
+    int e = 0;
+    for (int i = 0; i < 9; i++)
+        for (int j = i; j < 9; j++) A[9 * i + j] = A[9 * j + i] = N[e++];
+    for (int i = 0; i < 81; i++) V[i] = (i % 10 == 0) ? 1.0 : 0.0;
+}
+// g = the eigenvector of the smallest eigenvalue of A after kJacobiSweeps sweeps (A, V overwritten)
+inline void jacobi_host(double* A, double* V, double* g) {
+    for (int s = 0; s < kJacobiSweeps; s++) jacobi_sweep_host(A, V);
+    const int c = jacobi_min_index(A);
+    for (int k = 0; k < 9; k++) g[k] = V[9 * k + c];
+}
+
+inline double fold_lanes(double* part) {
+    for (int stride = kRefineLanes / 2; stride >= 1; stride >>= 1)
+        for (int l = 0; l < stride; l++) part[l] += part[l + stride];
+    return part[0];
+}
+
+// The normal matrix of the matches of pts (rows x1, y1, x2, y2) that are inliers of M: N[45] and
+// the normalisation.  False when the refit is invalid.
+template <int MODEL>
+inline bool refit_normal_host(const float* pts, int m, const float* M, float threshold,
+                              RefitNorm& nm, double* N) {
+    constexpr int S = MODEL == kModelF ? 8 : 4;
+    std::vector<uint8_t> in((size_t)m);
+    int n = 0;
+    for (int k = 0; k < m; k++) {
+        in[k] = inlier(MODEL, M, pts[4 * k], pts[4 * k + 1], pts[4 * k + 2], pts[4 * k + 3], threshold);
+        n += in[k];
+    }
+    if (n < S) return false;
+    std::vector<double> part((size_t)kRefineLanes * kNormalEntries, 0.0);
+    auto lane = [&](int e) { return part.data() + (size_t)e * kRefineLanes; };   // 64 partials of sum e
+    for (int k = 0; k < m; k++)
+        if (in[k])
+            for (int e = 0; e < 4; e++) lane(e)[k % kRefineLanes] += (double)pts[4 * k + e];
+    double sum[4];
+    for (int e = 0; e < 4; e++) sum[e] = fold_lanes(lane(e));
+    refit_centroids(sum, n, nm);
+    for (int e = 0; e < 2; e++) std::fill(lane(e), lane(e) + kRefineLanes, 0.0);
+    for (int k = 0; k < m; k++) {
+        if (!in[k]) continue;
+        double t1, t2;
+        refit_deviation(nm, (double)pts[4 * k], (double)pts[4 * k + 1], (double)pts[4 * k + 2],
+                        (double)pts[4 * k + 3], t1, t2);
+        lane(0)[k % kRefineLanes] += t1;
+        lane(1)[k % kRefineLanes] += t2;
+    }
+    const double dev1 = fold_lanes(lane(0)), dev2 = fold_lanes(lane(1));
+    if (!refit_scales(dev1, dev2, n, nm)) return false;
+    std::fill(part.begin(), part.end(), 0.0);
+    for (int k = 0; k < m; k++) {
+        if (!in[k]) continue;
+        double acc[kNormalEntries];
+        for (int e = 0; e < kNormalEntries; e++) acc[e] = lane(e)[k % kRefineLanes];
+        refit_accumulate<MODEL>(nm, (double)pts[4 * k], (double)pts[4 * k + 1], (double)pts[4 * k + 2],
+                                (double)pts[4 * k + 3], acc);
+        for (int e = 0; e < kNormalEntries; e++) lane(e)[k % kRefineLanes] = acc[e];
+    }
+    for (int e = 0; e < kNormalEntries; e++) N[e] = fold_lanes(lane(e));
+    return true;
+}
+
+// refit over the inliers of M: D = double[9] at unit Frobenius norm; false when invalid
+template <int MODEL>
+inline bool refit_host(const float* pts, int m, const float* M, float threshold, double* D) {
+    RefitNorm nm;
+    double N[kNormalEntries], A[81], V[81], g[9];
+    if (!refit_normal_host<MODEL>(pts, m, M, threshold, nm, N)) return false;
+    jacobi_start_host(N, A, V);
+    jacobi_host(A, V, g);
+    return refit_denormalise<MODEL>(nm, g, D);
+}
+
+// The round loop on one pair: M (float[9]) and its count c are the winner's, or an earlier
+// round's; returns the accepted rounds, *stop = why the loop ended (kStop*).
+template <int MODEL>
+inline int refine_pair_host(const float* pts, int m, float threshold, int rounds, float* M, int& c,
+                            int* stop) {
+    constexpr int S = MODEL == kModelF ? 8 : 4;
+    int done = 0, why = kStopBudget;
+    for (int r = 0; r < rounds; r++) {
+        if (c < S) {
+            why = kStopNoModel;
+            break;
+        }
+        double D[9];
+        if (!refit_host<MODEL>(pts, m, M, threshold, D)) {
+            why = kStopInvalid;
+            break;
+        }
+        float M2[9];
+        for (int i = 0; i < 9; i++) M2[i] = (float)D[i];
+        int c2 = 0;
+        bool changed = false;
+        for (int k = 0; k < m; k++) {
+            const float* q = pts + 4 * (size_t)k;
+            const bool a = inlier(MODEL, M, q[0], q[1], q[2], q[3], threshold);
+            const bool b = inlier(MODEL, M2, q[0], q[1], q[2], q[3], threshold);
+            c2 += b;
+            changed |= a != b;
+        }
+        if (c2 < c) {
+            why = kStopRejected;
+            break;
+        }
+        for (int i = 0; i < 9; i++) M[i] = M2[i];
+        c = c2;
+        done++;
+        if (!changed) {
+            why = kStopFixedPoint;
+            break;
+        }
+    }
+    if (stop) *stop = why;
+    return done;
+}
+
+// estimate_host followed by `rounds` rounds of refinement; rounds = 0 is estimate_host.
+// out_rounds / out_stop: [npairs], may be null.
+inline void refine_host(const float* loc, int loc_stride, const int64_t* set_offsets,
+                        const int* set_pairs, int npairs, const int* matches,
+                        const int* match_counts, int model, float threshold, int iterations,
+                        uint32_t seed, int rounds, float* out_models, int* out_inliers,
+                        uint8_t* out_mask, int* out_rounds, int* out_stop) {
+    estimate_host(loc, loc_stride, set_offsets, set_pairs, npairs, matches, match_counts, model,
+                  threshold, iterations, seed, out_models, out_inliers, out_mask);
+    std::vector<float> pts;
+    int64_t moff = 0;
+    for (int p = 0; p < npairs; p++) {
+        const int m = match_counts[p];
+        int done = 0, why = kStopBudget;
+        if (rounds > 0) {
+            const int64_t a0 = set_offsets[set_pairs[2 * p]], b0 = set_offsets[set_pairs[2 * p + 1]];
+            pts.resize((size_t)m * 4);
+            for (int k = 0; k < m; k++) {
+                const float* pa = loc + (a0 + matches[2 * (moff + k)]) * loc_stride;
+                const float* pb = loc + (b0 + matches[2 * (moff + k) + 1]) * loc_stride;
+                pts[4 * k] = pa[0];
+                pts[4 * k + 1] = pa[1];
+                pts[4 * k + 2] = pb[0];
+                pts[4 * k + 3] = pb[1];
+            }
+            float* M = out_models + 9 * (size_t)p;
+            done = model == kModelF
+                       ? refine_pair_host<kModelF>(pts.data(), m, threshold, rounds, M, out_inliers[p], &why)
+                       : refine_pair_host<kModelH>(pts.data(), m, threshold, rounds, M, out_inliers[p], &why);
+            if (done > 0 && out_mask)
+                for (int k = 0; k < m; k++)
+                    out_mask[moff + k] = inlier(model, M, pts[4 * k], pts[4 * k + 1], pts[4 * k + 2],
+                                                pts[4 * k + 3], threshold) ? 1 : 0;
+        }
+        if (out_rounds) out_rounds[p] = done;
+        if (out_stop) out_stop[p] = why;
         moff += m;
     }
 }

@@ -15,6 +15,9 @@
 //   k_estimate_finish   a workgroup per pair: regenerates the winner from its t, writes the
 //                       model, the mask and the count; a count that differs from the slot's is
 //                       reported through *err (a library error, never a device assert).
+//   k_estimate_refine   (sgpu_estimate_*_refined, rounds > 0) a 64-lane workgroup per pair: the
+//                       contract's round loop -- least-squares refit on the inliers, rescoring,
+//                       acceptance -- inside one launch, whatever the number of rounds.
 #include "sift_kernels.h"
 #include "sift_geom.h"
 
@@ -143,7 +146,189 @@ __global__ __launch_bounds__(256) void k_estimate_finish(const float4* __restric
     }
 }
 
+// a sum over the wave's 64 lanes, in every lane: lane l < stride gets v[l] + v[l + stride], as
+// sgeo::fold_lanes adds (the other lanes add the same two values the other way round)
+__device__ inline double fold_wave(double v) {
+#pragma unroll
+    for (int d = sgeo::kRefineLanes / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ inline int sum_wave(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// Local refinement (sift_geom.h, "local refinement"): one wave per pair runs the whole round loop.
+// Lane l takes the pair's rows l, l + 64, ..: the partial sums of the contract.  The normal matrix
+// and the eigenvectors live in LDS, row k the work of lane k < 9, so that the Jacobi rotations
+// index them at run time without a per-lane array; everything else is wave-uniform registers.
+// __syncthreads() in a one-wave workgroup is an LDS fence, no hardware barrier.
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_estimate_refine(const float4* __restrict__ pts,
+                                                        const sgeo::PairRec* __restrict__ pairs,
+                                                        float threshold, int rounds,
+                                                        float* __restrict__ models,
+                                                        int* __restrict__ inliers,
+                                                        uint8_t* __restrict__ mask,
+                                                        int* __restrict__ out_rounds) {
+    constexpr int S = MODEL == sgeo::kModelF ? 8 : 4;
+    __shared__ double s_A[81], s_V[81];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const sgeo::PairRec pr = pairs[p];
+    const float4* __restrict__ P = pts + pr.moff;
+    const int m = pr.m;
+    float M[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) M[i] = models[9 * (size_t)p + i];
+    int c = inliers[p];
+    int done = 0;
+    for (int r = 0; r < rounds && c >= S; r++) {
+        // the two centroids, then the two mean deviations, over the inliers of M
+        double sum[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = lane; k < m; k += 64) {
+            const float4 q = P[k];
+            if (sgeo::inlier(MODEL, M, q.x, q.y, q.z, q.w, threshold)) {
+                sum[0] += (double)q.x;
+                sum[1] += (double)q.y;
+                sum[2] += (double)q.z;
+                sum[3] += (double)q.w;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) sum[e] = fold_wave(sum[e]);
+        sgeo::RefitNorm nm;
+        sgeo::refit_centroids(sum, c, nm);
+        double dev1 = 0.0, dev2 = 0.0;
+        for (int k = lane; k < m; k += 64) {
+            const float4 q = P[k];
+            if (sgeo::inlier(MODEL, M, q.x, q.y, q.z, q.w, threshold)) {
+                double t1, t2;
+                sgeo::refit_deviation(nm, (double)q.x, (double)q.y, (double)q.z, (double)q.w, t1, t2);
+                dev1 += t1;
+                dev2 += t2;
+            }
+        }
+        dev1 = fold_wave(dev1);
+        dev2 = fold_wave(dev2);
+        if (!sgeo::refit_scales(dev1, dev2, c, nm)) break;
+        // the normal matrix
+        double N[sgeo::kNormalEntries];
+#pragma unroll
+        for (int e = 0; e < sgeo::kNormalEntries; e++) N[e] = 0.0;
+        for (int k = lane; k < m; k += 64) {
+            const float4 q = P[k];
+            if (sgeo::inlier(MODEL, M, q.x, q.y, q.z, q.w, threshold))
+                sgeo::refit_accumulate<MODEL>(nm, (double)q.x, (double)q.y, (double)q.z, (double)q.w, N);
+        }
+#pragma unroll
+        for (int e = 0; e < sgeo::kNormalEntries; e++) N[e] = fold_wave(N[e]);
+        // every lane holds all of N: lane 0 spreads it over both triangles of A
+        __syncthreads();   // (the reads of the round before are done)
+        if (lane == 0) {
+            int e = 0;
+#pragma unroll
+            for (int i = 0; i < 9; i++) {
+#pragma unroll
+                for (int j = i; j < 9; j++) {
+                    s_A[9 * i + j] = N[e];
+                    s_A[9 * j + i] = N[e];
+                    e++;
+                }
+            }
+        }
+        for (int i = lane; i < 81; i += 64) s_V[i] = (i % 10 == 0) ? 1.0 : 0.0;
+        __syncthreads();
+        // cyclic Jacobi, sgeo::jacobi_sweep_host with its loop over k spread over lanes 0 .. 8
+        const int k = lane < 9 ? lane : 8;
+        for (int sweep = 0; sweep < sgeo::kJacobiSweeps; sweep++) {
+            for (int jp = 0; jp < 8; jp++) {
+                for (int jq = jp + 1; jq < 9; jq++) {
+                    const double app = s_A[10 * jp], aqq = s_A[10 * jq], apq = s_A[9 * jp + jq];
+                    const double akp = s_A[9 * k + jp], akq = s_A[9 * k + jq];
+                    const double vkp = s_V[9 * k + jp], vkq = s_V[9 * k + jq];
+                    __syncthreads();
+                    if (apq != 0.0 && lane < 9) {
+                        const sgeo::JacobiRot rot = sgeo::jacobi_rotation(app, aqq, apq);
+                        double x, y;
+                        sgeo::jacobi_apply(rot, vkp, vkq, x, y);
+                        s_V[9 * k + jp] = x;
+                        s_V[9 * k + jq] = y;
+                        if (k == jp) {
+                            s_A[10 * jp] = sgeo::jacobi_app(rot, app, apq);
+                            s_A[9 * jp + jq] = 0.0;
+                        } else if (k == jq) {
+                            s_A[10 * jq] = sgeo::jacobi_aqq(rot, aqq, apq);
+                            s_A[9 * jq + jp] = 0.0;
+                        } else {
+                            sgeo::jacobi_apply(rot, akp, akq, x, y);
+                            s_A[9 * k + jp] = x;
+                            s_A[9 * jp + k] = x;
+                            s_A[9 * k + jq] = y;
+                            s_A[9 * jq + k] = y;
+                        }
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+        const int col = sgeo::jacobi_min_index(s_A);
+        double g[9], D[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) g[i] = s_V[9 * i + col];
+        if (!sgeo::refit_denormalise<MODEL>(nm, g, D)) break;
+        float M2[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) M2[i] = (float)D[i];
+        // score M', and whether any match changed side
+        int c2 = 0;
+        bool changed = false;
+        for (int kk = lane; kk < m; kk += 64) {
+            const float4 q = P[kk];
+            const bool a = sgeo::inlier(MODEL, M, q.x, q.y, q.z, q.w, threshold);
+            const bool b = sgeo::inlier(MODEL, M2, q.x, q.y, q.z, q.w, threshold);
+            c2 += b ? 1 : 0;
+            changed |= a != b;
+        }
+        c2 = sum_wave(c2);
+        if (c2 < c) break;
+#pragma unroll
+        for (int i = 0; i < 9; i++) M[i] = M2[i];
+        c = c2;
+        done++;
+        if (__ballot(changed) == 0ull) break;
+    }
+    if (lane == 0) out_rounds[p] = done;
+    if (done == 0) return;
+    // accepted: the model, its count and its mask replace the winner's
+    if (lane < 9) {
+        float v = M[0];
+#pragma unroll
+        for (int i = 1; i < 9; i++) v = lane == i ? M[i] : v;
+        models[9 * (size_t)p + lane] = v;
+    }
+    if (lane == 0) inliers[p] = c;
+    if (mask)
+        for (int k = lane; k < m; k += 64) {
+            const float4 q = P[k];
+            mask[pr.moff + k] = sgeo::inlier(MODEL, M, q.x, q.y, q.z, q.w, threshold) ? 1 : 0;
+        }
+}
+
 }  // namespace
+
+hipError_t launch_estimate_refine(const float4* pts, const sgeo::PairRec* pairs, int npairs,
+                                  int model, float threshold, int rounds, float* models,
+                                  int* inliers, uint8_t* mask, int* out_rounds, hipStream_t stream) {
+    if (npairs <= 0 || rounds <= 0) return hipSuccess;
+    if (model == sgeo::kModelF)
+        hipLaunchKernelGGL(k_estimate_refine<sgeo::kModelF>, dim3(npairs), dim3(64), 0, stream, pts,
+                           pairs, threshold, rounds, models, inliers, mask, out_rounds);
+    else
+        hipLaunchKernelGGL(k_estimate_refine<sgeo::kModelH>, dim3(npairs), dim3(64), 0, stream, pts,
+                           pairs, threshold, rounds, models, inliers, mask, out_rounds);
+    return hipGetLastError();
+}
 
 hipError_t launch_estimate_gather(const float* loc, int loc_stride, const sgeo::PairRec* pairs,
                                   int npairs, const int* matches, long long total, float4* pts,

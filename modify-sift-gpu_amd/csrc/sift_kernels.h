@@ -491,4 +491,11 @@ hipError_t launch_estimate_finish(const float4* pts, const sgeo::PairRec* pairs,
                                   int model, float threshold, uint32_t seed,
                                   const unsigned long long* slots, float* models, int* inliers,
                                   uint8_t* mask, int* err, hipStream_t stream);
+// One 64-lane workgroup per pair, after launch_estimate_finish: up to `rounds` rounds of
+// sgeo::refine_pair_host on models[p] / inliers[p].  rounds_done[p] = the accepted rounds; models,
+// inliers and mask (may be null) are rewritten for the pairs that accepted one.  rounds <= 0:
+// nothing is launched (and rounds_done is not written).
+hipError_t launch_estimate_refine(const float4* pts, const sgeo::PairRec* pairs, int npairs,
+                                  int model, float threshold, int rounds, float* models,
+                                  int* inliers, uint8_t* mask, int* rounds_done, hipStream_t stream);
 }  // namespace sgk

@@ -39,6 +39,7 @@ C_API = [
     "sgpu_debug_set_duo_strips", "sgpu_debug_pyramid_plan", "sgpu_debug_set_feature_queue",
     "sgpu_match_batch_guided", "sgpu_match_images_guided",
     "sgpu_estimate_batch", "sgpu_estimate_images",
+    "sgpu_estimate_batch_refined", "sgpu_estimate_images_refined",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -129,6 +130,11 @@ def lib():
                                           c.c_float, c.c_int, c.c_uint32, vp, vp, vp, c.c_int]
         L.sgpu_estimate_images.argtypes = [vp, vp, c.c_int, vp, vp, c.c_int, c.c_float, c.c_int,
                                            c.c_uint32, vp, vp, vp]
+        L.sgpu_estimate_batch_refined.argtypes = [vp, vp, vp, c.c_int, vp, c.c_int, vp, vp,
+                                                  c.c_int, c.c_float, c.c_int, c.c_uint32,
+                                                  c.c_int, vp, vp, vp, vp, c.c_int]
+        L.sgpu_estimate_images_refined.argtypes = [vp, vp, c.c_int, vp, vp, c.c_int, c.c_float,
+                                                   c.c_int, c.c_uint32, c.c_int, vp, vp, vp, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -656,10 +662,12 @@ class SiftContext:
 
     MODELS = {"H": 0, "F": 1}   # SGPU_MODEL_HOMOGRAPHY / SGPU_MODEL_FUNDAMENTAL
 
-    def _estimate(self, call, pairs, matches, model, threshold, iterations, seed):
-        """Common part of estimate_batch / estimate_images: the pair list and the per-pair [m, 2]
-        match arrays go down concatenated; (models [npairs][3][3] float32, inliers [npairs]
-        int32, masks: one bool array per pair) come back."""
+    def _estimate(self, call, pairs, matches, model, threshold, iterations, seed, rounds=None):
+        """Common part of estimate_batch / estimate_images and their refined forms: the pair list
+        and the per-pair [m, 2] match arrays go down concatenated; (models [npairs][3][3] float32,
+        inliers [npairs] int32, masks: one bool array per pair) come back, and with rounds (the
+        refined forms: call takes the round budget and the output array last) the accepted rounds
+        [npairs] int32 as a fourth."""
         if model not in self.MODELS:
             raise ValueError(f'model must be "H" or "F", got {model!r}')
         pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
@@ -674,14 +682,17 @@ class SiftContext:
         models = np.zeros((max(npairs, 1), 9), np.float32)
         inliers = np.zeros(max(npairs, 1), np.int32)
         mask = np.zeros(max(total, 1), np.uint8)
+        done = np.zeros(max(npairs, 1), np.int32)
+        extra = () if rounds is None else (int(rounds), done.ctypes.data)
         rc = call(pr.ctypes.data if npairs else None, npairs, cat.ctypes.data if total else None,
                   counts.ctypes.data if npairs else None, self.MODELS[model], float(threshold),
                   int(iterations), int(seed) & 0xFFFFFFFF, models.ctypes.data, inliers.ctypes.data,
-                  mask.ctypes.data)
+                  mask.ctypes.data, *extra)
         self._check(rc, "estimate")
         offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
         masks = [mask[offs[p]:offs[p + 1]].astype(bool) for p in range(npairs)]
-        return models[:npairs].reshape(npairs, 3, 3).copy(), inliers[:npairs].copy(), masks
+        out = (models[:npairs].reshape(npairs, 3, 3).copy(), inliers[:npairs].copy(), masks)
+        return out if rounds is None else out + (done[:npairs].copy(),)
 
     def estimate_batch(self, loc: np.ndarray, offsets, pairs, matches, model="H", threshold=2.0,
                        iterations=512, seed=0, device_ptr=None):
@@ -692,20 +703,48 @@ class SiftContext:
         [npairs][3][3] float32 at unit Frobenius norm, ready for match_batch_guided; inlier counts
         [npairs]; one bool mask per pair).  A pair without a model has zeros.  device_ptr: the
         int device address of the locations, read in place (SGPU_INPUT_DEVICE; loc is ignored)."""
-        off = np.ascontiguousarray(offsets, np.int64)
-        nsets = len(off) - 1
-        if device_ptr is not None:
-            ptr, flags = ctypes.c_void_p(device_ptr), SGPU_INPUT_DEVICE
-        else:
-            lc = np.ascontiguousarray(loc, np.float32)
-            if lc.ndim != 2 or lc.shape[1] != 2 or nsets < 0 or (len(off) and off[-1] > len(lc)):
-                raise ValueError(f"locations must be [rows][2] covering the offsets, got {lc.shape}")
-            ptr, flags = (lc.ctypes.data if len(lc) else None), SGPU_INPUT_HOST
+        off, nsets, lc, ptr, flags = self._estimate_sets(loc, offsets, device_ptr)
 
         def call(pr, npairs, cat, counts, mdl, thr, it, sd, models, inliers, mask):
             return lib().sgpu_estimate_batch(self._ctx, ptr, off.ctypes.data, nsets, pr, npairs, cat,
                                              counts, mdl, thr, it, sd, models, inliers, mask, flags)
         return self._estimate(call, pairs, matches, model, threshold, iterations, seed)
+
+    @staticmethod
+    def _estimate_sets(loc, offsets, device_ptr):
+        """The set arguments of estimate_batch: (offsets int64, nsets, the host array kept alive,
+        the locations' pointer, the input flag)."""
+        off = np.ascontiguousarray(offsets, np.int64)
+        nsets = len(off) - 1
+        if device_ptr is not None:
+            return off, nsets, None, ctypes.c_void_p(device_ptr), SGPU_INPUT_DEVICE
+        lc = np.ascontiguousarray(loc, np.float32)
+        if lc.ndim != 2 or lc.shape[1] != 2 or nsets < 0 or (len(off) and off[-1] > len(lc)):
+            raise ValueError(f"locations must be [rows][2] covering the offsets, got {lc.shape}")
+        return off, nsets, lc, (lc.ctypes.data if len(lc) else None), SGPU_INPUT_HOST
+
+    def estimate_batch_refined(self, loc: np.ndarray, offsets, pairs, matches, model="H",
+                               threshold=2.0, iterations=512, seed=0, rounds=3, device_ptr=None):
+        """estimate_batch, then up to `rounds` (0 .. 16) least-squares refits of every pair's model
+        on its own inliers, on the device (sgpu_estimate_batch_refined): a refit that would lose
+        an inlier is rejected, so no count falls below estimate_batch's, and every mask is still
+        the guided test of its returned matrix.  Returns (models, inliers, masks, rounds): the
+        last = the accepted rounds of every pair, int32 [npairs]."""
+        off, nsets, lc, ptr, flags = self._estimate_sets(loc, offsets, device_ptr)
+
+        def call(pr, npairs, cat, counts, mdl, thr, it, sd, models, inliers, mask, budget, done):
+            return lib().sgpu_estimate_batch_refined(self._ctx, ptr, off.ctypes.data, nsets, pr,
+                                                     npairs, cat, counts, mdl, thr, it, sd, budget,
+                                                     models, inliers, mask, done, flags)
+        return self._estimate(call, pairs, matches, model, threshold, iterations, seed, rounds)
+
+    def estimate_images_refined(self, pairs, matches, model="H", threshold=2.0, iterations=512,
+                                seed=0, rounds=3):
+        """estimate_batch_refined over the last extract (sgpu_estimate_images_refined)."""
+        def call(pr, npairs, cat, counts, mdl, thr, it, sd, models, inliers, mask, budget, done):
+            return lib().sgpu_estimate_images_refined(self._ctx, pr, npairs, cat, counts, mdl, thr,
+                                                      it, sd, budget, models, inliers, mask, done)
+        return self._estimate(call, pairs, matches, model, threshold, iterations, seed, rounds)
 
     def estimate_images(self, pairs, matches, model="H", threshold=2.0, iterations=512, seed=0):
         """estimate_batch over the last extract (sgpu_estimate_images): pairs of its images, matches
