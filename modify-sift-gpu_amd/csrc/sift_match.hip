@@ -158,12 +158,18 @@ __global__ __launch_bounds__(256) void k_prep_set(const uint4* __restrict__ src,
         for (int i = blockIdx.x * 256 + threadIdx.x; i < kCtPad; i += (int)stride) ctfill[n + i] = kCtMissing;
 }
 
+// RowMatch_Kernel's rank of a column among equal maxima (lower wins): thread t = col % 32 scans
+// columns t, t + 32, ...; the tree reduction (steps 16, 8, 4, 2, 1, the lower slot kept on equal
+// values) merges two threads at the step of their lowest differing bit, where the one with that
+// bit clear wins -- the order of the 5 bits of t reversed (ProgramCU.cu:1823-1835).
+__device__ __forceinline__ int row_tie_rank(int col) { return (int)(__brev((unsigned)col) >> 27); }
+
 // Equal-dot order of the two decisions: does column a come before column b (-1 = none)?
 template <bool TIE32>
 __device__ __forceinline__ bool tie_before(int a, int b) {
     if (a < 0) return false;
     if (b < 0) return true;
-    if (TIE32 && (a & 31) != (b & 31)) return (a & 31) < (b & 31);
+    if (TIE32 && (a & 31) != (b & 31)) return row_tie_rank(a) < row_tie_rank(b);
     return a < b;
 }
 
@@ -184,11 +190,12 @@ __device__ __forceinline__ bool tie_before(int a, int b) {
 // bit 4+i = no row of its 8-row block of set 1 passes.  One dwordx4 load per lane and tile.
 //
 // Equal dots: the column side (A = set 2) takes the lowest column (ColMatch's row order); the
-// row side (A = set 1, TIE32) takes the column lowest mod 32, then the lowest, as RowMatch_Kernel's
-// 32 strided threads and tree reduction do (ProgramCU.cu:1803-1835).  Inside a tile the key's 7
+// row side (A = set 1, TIE32) takes the column whose col % 32 has the lowest rank (row_tie_rank:
+// its 5 bits reversed), then the lowest, as RowMatch_Kernel's 32 strided threads and tree
+// reduction do (ProgramCU.cu:1803-1835).  Inside a tile the key's 7
 // low bits order equal dots that way, so the tile's maximum key is its winner.  Across tiles a
 // later tile may only take over when the key's tie-relevant prefix grows (the dot; TIE32: the dot
-// and col % 32), and the key is recorded with its tile at that moment.
+// and the rank of col % 32), and the key is recorded with its tile at that moment.
 //
 // COLS (mutual matching, one GEMM for both decisions): every tile also yields the column side
 // (ColMatch_Kernel's decision over set-1 rows, ProgramCU.cu:1844-1900, fed by
@@ -318,12 +325,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? SGK_M
     };
 
     // the key's low 7 bits per column block: a larger value = an earlier column in the
-    // reference's tie order (TIE32: (31 - col % 32) << 2 | (3 - col / 32 in the tile); else
-    // 127 - col in the tile)
+    // reference's tie order (TIE32: (31 - rank of col % 32) << 2 | (3 - col / 32 in the tile);
+    // else 127 - col in the tile)
     int low[8];
 #pragma unroll
     for (int cb = 0; cb < 8; cb++)
-        low[cb] = TIE32 ? ((31 - ((cb & 1) * 16 + l16)) << 2) | (3 - (cb >> 1))
+        low[cb] = TIE32 ? ((31 - row_tie_rank((cb & 1) * 16 + l16)) << 2) | (3 - (cb >> 1))
                         : 127 - (cb * 16 + l16);
 
     // Tile j is computed from LDS buffer j & 1.  kPf = 2 (RAW): tile j + 2's loads are issued
@@ -575,7 +582,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? SGK_M
 #endif
             } else {
                 const int k = W[rb][i] & 127;
-                const int in_tile = TIE32 ? (3 - (k & 3)) * 32 + (31 - (k >> 2)) : 127 - k;
+                const int in_tile = TIE32 ? (3 - (k & 3)) * 32 + row_tie_rank(31 - (k >> 2)) : 127 - k;
                 I[rb][i] = I[rb][i] < 0 ? -1 : I[rb][i] + in_tile;
                 M[rb][i] >>= 7;
                 S[rb][i] >>= 7;

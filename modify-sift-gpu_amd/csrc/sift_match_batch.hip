@@ -15,8 +15,8 @@
 // signed i8 MFMA (v_mfma_i32_16x16x64_i8) applies; dot(u1, u2) = dot(s1, s2) + 128*sum(u1) +
 // 128*sum(u2) - 2^21, all in int32.  The column term enters the key, the row term is added once
 // per row in the finish.  Every value is folded as the key ((acc + column term) << 7) | low, whose
-// 7 low bits order equal dots as the reference does (direction 0: lowest column mod 32, then
-// lowest, RowMatch_Kernel; direction 1: lowest column, i.e. ColMatch_Kernel's lowest row of set
+// 7 low bits order equal dots as the reference does (direction 0: lowest rank of the column mod 32
+// (row_tie_rank), then lowest, RowMatch_Kernel; direction 1: lowest column, i.e. ColMatch_Kernel's lowest row of set
 // 1), so the results are exact for every ratiomax.
 //
 // Set boundaries: the sets lie back to back in one buffer, so the bytes after set B's last row are
@@ -69,11 +69,16 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
     return max(min(a, b), min(max(a, b), c));
 }
 
+// RowMatch_Kernel's rank of a column among equal maxima, lower wins: the 5 bits of col % 32
+// reversed (its tree reduction merges two threads at their lowest differing bit and keeps the
+// one with that bit clear; k_match_rows, sift_match.hip).
+__device__ __forceinline__ int row_tie_rank(int col) { return (int)(__brev((unsigned)col) >> 27); }
+
 // Equal-dot order of the two directions: does column a come before column b (-1 = none)?
 __device__ __forceinline__ bool tie_before(bool tie32, int a, int b) {
     if (a < 0) return false;
     if (b < 0) return true;
-    if (tie32 && (a & 31) != (b & 31)) return (a & 31) < (b & 31);
+    if (tie32 && (a & 31) != (b & 31)) return row_tie_rank(a) < row_tie_rank(b);
     return a < b;
 }
 
@@ -274,12 +279,12 @@ __device__ __forceinline__ void match_pairs_item(const uint8_t* __restrict__ S,
     };
 
     // the key's low 7 bits per column block: a larger value = an earlier column in the
-    // direction's tie order (tie32: (31 - col % 32) << 2 | (3 - col / 32 in the tile); else
-    // 127 - col in the tile)
+    // direction's tie order (tie32: (31 - rank of col % 32) << 2 | (3 - col / 32 in the tile);
+    // else 127 - col in the tile)
     int low[8];
 #pragma unroll
     for (int cb = 0; cb < 8; cb++)
-        low[cb] = tie32 ? ((31 - ((cb & 1) * 16 + l16)) << 2) | (3 - (cb >> 1))
+        low[cb] = tie32 ? ((31 - row_tie_rank((cb & 1) * 16 + l16)) << 2) | (3 - (cb >> 1))
                         : 127 - (cb * 16 + l16);
 
     // tile j is computed from LDS buffer j & 1; tile j + 1 is loaded and stored within tile j
@@ -405,7 +410,7 @@ __device__ __forceinline__ void match_pairs_item(const uint8_t* __restrict__ S,
                         mt[rb][i] = max(mt[rb][i], key);
                     }
         // a later tile takes over only when the key's tie-relevant prefix grows (the dot; tie32:
-        // the dot and col % 32); the key is recorded with its tile at that moment
+        // the dot and the rank of col % 32); the key is recorded with its tile at that moment
 #pragma unroll
         for (int rb = 0; rb < 2; rb++)
 #pragma unroll
@@ -432,7 +437,7 @@ __device__ __forceinline__ void match_pairs_item(const uint8_t* __restrict__ S,
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int k = W[rb][i] & 127;
-            const int in_tile = tie32 ? (3 - (k & 3)) * 32 + (31 - (k >> 2)) : 127 - k;
+            const int in_tile = tie32 ? (3 - (k & 3)) * 32 + row_tie_rank(31 - (k >> 2)) : 127 - k;
             I[rb][i] = I[rb][i] < 0 ? -1 : I[rb][i] + in_tile;
             M[rb][i] >>= 7;
             S2[rb][i] >>= 7;

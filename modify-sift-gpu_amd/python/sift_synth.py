@@ -168,6 +168,8 @@ def synth_tie_scene(n1: int, n2: int, seed: int, col_pairs, row_pairs=()):
     return q1, q2, rows
 
 
-def tie_winner(ca: int, cb: int) -> int:
-    """RowMatch_Kernel's choice between two equal maxima: lowest column mod 32, then lowest."""
-    return min((ca, cb), key=lambda c: (c % 32, c))
+def tie_winner(*cols: int) -> int:
+    """RowMatch_Kernel's choice among columns with equal maxima: thread t = column mod 32 holds the
+    first of its columns, and the tree reduction keeps, of two threads, the one whose lowest
+    differing bit is clear -- the lowest t with its 5 bits reversed; then the lowest column."""
+    return min(cols, key=lambda c: (int(format(c % 32, "05b")[::-1], 2), c))

@@ -187,11 +187,13 @@ struct Key4 { float x, y, z, w; };
 //   3  a peak may equal the bin before it (>=)
 //   4  the one-orientation maximum moves to a later equal bin (>=)
 //   6  the first test against the row neighbours is strict (<, >)
+//   7  RowMatch_Kernel's equal maxima go to the lowest column mod 32 (not the reduction's order)
 #ifndef ORACLE_TIE_VARIANT
 #define ORACLE_TIE_VARIANT 0
 #endif
 constexpr int kTie = ORACLE_TIE_VARIANT;
-static_assert(kTie == 0 || kTie == 1 || kTie == 2 || kTie == 3 || kTie == 4 || kTie == 6,
+static_assert(kTie == 0 || kTie == 1 || kTie == 2 || kTie == 3 || kTie == 4 || kTie == 6 ||
+                  kTie == 7,
               "ORACLE_TIE_VARIANT");
 
 // --- ComputeKEY_Kernel (ProgramCU.cu:553-671) with READ_CMP_DOG_DATA (:534-550).
@@ -678,7 +680,7 @@ void limit_feature_count(std::vector<int>& cnt, int T, int method, bool list_sta
 }  // namespace
 
 Result extract(const uint8_t* img, int w, int h, int stride, const sgpu_options& opt,
-               bool keep, const float* img_f32) {
+               bool keep, const float* img_f32, bool keep_stages) {
     // first octave: -fo, -prep and -maxd (sgp::plan_input restates GLTexImage.cpp:928-960 and
     // PyramidCU.cpp:89-135)
     const sgp::InputPlan plan = sgp::plan_input(w, h, std::max(-3, opt.octave_min),
@@ -750,6 +752,15 @@ Result extract(const uint8_t* img, int w, int h, int stride, const sgpu_options&
             L.candidates = histo_list(key, oc.wa, oc.h, hp_levels);
             for (const Candidate& c : L.candidates)
                 sign[o * d + j].push_back(key[(size_t)c.row * oc.wa + c.col].x);
+            if (keep_stages) {
+                L.tdog = S.dog_threshold;
+                L.tedge = S.edge_threshold;
+                for (int m = 1; m <= 3; m++)
+                    L.dog.insert(L.dog.end(), dog[m + j].px.begin(), dog[m + j].px.end());
+                L.grad = gr[1 + j];
+                L.key.resize(key.size() * 4);
+                memcpy(L.key.data(), key.data(), key.size() * sizeof(Key4));
+            }
             R.levels.push_back(std::move(L));
         }
         for (int j = 0; j < d; j++) grad[o].push_back(std::move(gr[1 + j]));
@@ -772,6 +783,8 @@ Result extract(const uint8_t* img, int w, int h, int stride, const sgpu_options&
         const int o = L.octave, j = L.level;
         const sgp::Octave& oc = R.octaves[o];
         const float sigma = sgp::level_sigma(S, j + S.level_min + 1);
+        L.sigma = sigma;
+        L.sigma_step = sigma_step;
         L.oriented.resize(L.candidates.size() * 4);
         for (size_t f = 0; f < L.candidates.size(); f++) {
             orientation(L.candidates[f], grad[o][j], oc.wa, oc.h, sigma, sigma_step,
@@ -952,14 +965,25 @@ std::vector<float> describe_keys(const uint8_t* img, int w, int h, int stride,
 struct Top2 { int max = 0, idx = -1, second = 0; };
 
 // RowMatch_Kernel (ProgramCU.cu:1785-1835): 32 threads, thread t scans columns t, t+32, ... with
-// a running (max, second, idx) from (0, 0, -1) and strict '>'; a tree reduction then keeps the
-// lower thread on equal maxima, and the second is the largest value except the winner.  In
-// column order that is: a larger value wins; an equal value takes the index when its column is
-// lower mod 32 (same thread: the first occurrence stays); the second collects every other value.
+// a running (max, second, idx) from (0, 0, -1) and strict '>'; a tree reduction (steps 16, 8, 4,
+// 2, 1) then keeps the lower slot on equal maxima, and the second is the largest value except
+// the winner.  Two threads with equal maxima meet at the step of their lowest differing bit, and
+// the one with that bit clear is kept: among equal maxima the thread whose 5 bits, reversed,
+// give the lowest number wins (threads 8 and 2 meet at step 2 in slots 0 and 2: 8 wins) -- not
+// the lowest thread, which is what this function assumed until the reference's own kernel, run
+// on the CPU, was compared (tests/test_ref_kernels.py; that rule is kept as tie variant 7).  In
+// column order: a larger value wins; an equal value takes the index when its thread ranks
+// lower (same thread: the first occurrence stays); the second collects every other value.
+inline int row_tie_rank(int col) {
+    if (kTie == 7) return col & 31;
+    int r = 0;
+    for (int b = 0; b < 5; b++) r |= ((col >> b) & 1) << (4 - b);
+    return r;
+}
 inline void row_fold(Top2& t, int v, int col) {
     if (v > t.max) { t.second = t.max; t.max = v; t.idx = col; return; }
     t.second = std::max(t.second, v);
-    if (v == t.max && t.idx >= 0 && (col & 31) < (t.idx & 31)) t.idx = col;
+    if (v == t.max && t.idx >= 0 && row_tie_rank(col) < row_tie_rank(t.idx)) t.idx = col;
 }
 
 // MultiplyDescriptor(G)_Kernel's column partials + ColMatch_Kernel (ProgramCU.cu:1540-1552,
@@ -1309,6 +1333,111 @@ int oracle_features_oct(const uint8_t* img, int w, int h, int stride, const sgpu
 
 // SiftGPU::RunSIFT(num, keys, keys_have_orientation) on image img: keys_out [num][4],
 // desc [num][128] in input order.
+// The stages of level `level` of octave `octave` (Result::levels with keep_stages): dims =
+// {wa, h, candidate count}, sig = {sigma, sigma_step, ComputeKEY's Tdog, Tedge}; dog 3 x wa x h, grad wa x h x 2, key
+// wa x h x 4, list (col, row, 0, 0) and oriented 4 per candidate, up to cap.  Every output may
+// be null.  Returns the candidate count, -1 for a level that does not exist.
+int oracle_level_stages(const uint8_t* img, int w, int h, int stride, const sgpu_options* opt,
+                        int octave, int level, int* dims, float* sig, float* dog, float* grad,
+                        float* key, int* list, float* oriented, int cap) {
+    oracle::Result R = oracle::extract(img, w, h, stride, *opt, false, nullptr, true);
+    for (const oracle::LevelResult& L : R.levels) {
+        if (L.octave != octave || L.level != level) continue;
+        const int n = (int)L.candidates.size();
+        if (dims) { dims[0] = R.octaves[octave].wa; dims[1] = R.octaves[octave].h; dims[2] = n; }
+        if (sig) { sig[0] = L.sigma; sig[1] = L.sigma_step; sig[2] = L.tdog; sig[3] = L.tedge; }
+        if (dog) memcpy(dog, L.dog.data(), L.dog.size() * sizeof(float));
+        if (grad) memcpy(grad, L.grad.data(), L.grad.size() * sizeof(float));
+        if (key) memcpy(key, L.key.data(), L.key.size() * sizeof(float));
+        for (int i = 0; i < n && i < cap; i++) {
+            if (list) { list[4 * i] = L.candidates[i].col; list[4 * i + 1] = L.candidates[i].row; list[4 * i + 2] = list[4 * i + 3] = 0; }
+            if (oriented) memcpy(oriented + 4 * i, &L.oriented[4 * i], 4 * sizeof(float));
+        }
+        return n;
+    }
+    return -1;
+}
+
+// ---- single stages on caller-supplied inputs (tests/test_ref_kernels.py feeds the same arrays
+//      to the reference's own kernels).  Images are row-major w x h.
+static oracle::Image stage_image(const float* px, int w, int h) {
+    oracle::Image im;
+    im.w = w;
+    im.h = h;
+    im.px.assign(px, px + (size_t)w * h);
+    return im;
+}
+
+// FilterImage(sigma): returns the filter width.
+int oracle_stage_filter(const float* src, int w, int h, float sigma, float width_factor,
+                        float* dst) {
+    float taps[sgp::kMaxFilterWidth];
+    const int fw = sgp::make_filter(sigma, width_factor, taps);
+    const oracle::Image out = oracle::filter(stage_image(src, w, h), taps, fw);
+    memcpy(dst, out.px.data(), out.px.size() * sizeof(float));
+    return fw;
+}
+
+// ComputeDOG: dog = cur - prev and, unless grad is null, the float2 gradient of cur.
+void oracle_stage_dog(const float* prev, const float* cur, int w, int h, float* dog, float* grad) {
+    oracle::Image d;
+    std::vector<float> g;
+    oracle::compute_dog(stage_image(cur, w, h), stage_image(prev, w, h), &d, grad ? &g : nullptr);
+    memcpy(dog, d.px.data(), d.px.size() * sizeof(float));
+    if (grad) memcpy(grad, g.data(), g.size() * sizeof(float));
+}
+
+// ComputeKEY(dog, key, Tdog, Tedge) with the arguments ProgramCU::ComputeKEY takes.
+void oracle_stage_key(const float* dp, const float* dc, const float* dn, int w, int h, float tdog,
+                      float tedge, int subpixel, float* key) {
+    std::vector<oracle::Key4> k;
+    oracle::compute_key(stage_image(dp, w, h), stage_image(dc, w, h), stage_image(dn, w, h),
+                        (subpixel ? 0.8f : 1.0f) * tdog, tdog, (tedge + 1) * (tedge + 1) / tedge,
+                        subpixel, &k);
+    memcpy(key, k.data(), k.size() * sizeof(oracle::Key4));
+}
+
+// The per-level list (col, row, 0, 0) of a key image inside a pyramid whose base level is
+// base_w x base_h; returns the count (entries beyond cap are not written).
+int oracle_stage_list(const float* key, int w, int h, int base_w, int base_h, int* list, int cap) {
+    std::vector<oracle::Key4> k((size_t)w * h);
+    memcpy(k.data(), key, k.size() * sizeof(oracle::Key4));
+    const int levels = (int)std::ceil(std::log(double(std::max(base_w, base_h))) / std::log(4.0));
+    const std::vector<oracle::Candidate> c = oracle::histo_list(k, w, h, levels);
+    for (int i = 0; i < (int)c.size() && i < cap; i++) {
+        list[4 * i] = c[i].col;
+        list[4 * i + 1] = c[i].row;
+        list[4 * i + 2] = list[4 * i + 3] = 0;
+    }
+    return (int)c.size();
+}
+
+// ComputeOrientation on list entries (col, row, ., .) with the key image's offsets: out 4 per
+// entry (x, y, scale, packed orientations -- or the angle for num_orientation == 1).
+void oracle_stage_orientation(const int* list, int n, const float* key, const float* grad, int w,
+                              int h, float sigma, float sigma_step, float gaussian_factor,
+                              float window_factor, int num_orientation, int subpixel, float* out) {
+    const std::vector<float> g(grad, grad + (size_t)w * h * 2);
+    for (int i = 0; i < n; i++) {
+        const float* k = key + 4 * ((size_t)list[4 * i + 1] * w + list[4 * i]);
+        const oracle::Candidate c{list[4 * i], list[4 * i + 1], k[1], k[2], k[3]};
+        oracle::orientation(c, g, w, h, sigma, sigma_step, gaussian_factor,
+                            gaussian_factor * window_factor, num_orientation, subpixel, 0, 0,
+                            out + 4 * i);
+    }
+}
+
+// ComputeDescriptor for n keys (x, y, scale, orientation) in octave coordinates; rect: the RECT
+// kernel on (x, y, width, height).
+void oracle_stage_descriptor(const float* keys, int n, const float* grad, int w, int h,
+                             float window_factor, int normalized, int rect, float* out) {
+    const std::vector<float> g(grad, grad + (size_t)w * h * 2);
+    for (int i = 0; i < n; i++) {
+        if (rect) oracle::descriptor_rect(keys + 4 * i, g, w, h, normalized, out + 128 * (size_t)i);
+        else oracle::descriptor(keys + 4 * i, g, w, h, window_factor, normalized, out + 128 * (size_t)i);
+    }
+}
+
 int oracle_describe_keys(const uint8_t* img, int w, int h, int stride, const sgpu_options* opt,
                          const float* keys, int num, int has_orientation, float* keys_out,
                          float* desc) {
@@ -1369,6 +1498,19 @@ void oracle_schedule(int dog_level_num, float* sigma0, float* sigma_skip0, float
         sigmas[i] = S.sigma[i];
         widths[i + 1] = sgp::make_filter(S.sigma[i], 4.0f, taps);
     }
+}
+
+// Every sigma FilterImage is called with for dog_level_num levels (first octave 0): the initial
+// smoothing, the smoothing after an octave change (0 = none) and the level-to-level sigmas.
+int oracle_filter_sigmas(int dog_level_num, float* out, int max) {
+    sgp::Options po;
+    po.dog_level_num = dog_level_num;
+    const sgp::Schedule S = sgp::make_schedule(po);
+    int n = 0;
+    if (n < max) out[n++] = S.initial_smooth;
+    if (n < max) out[n++] = S.sigma_skip1;
+    for (int i = 0; i < S.level_num - 1 && n < max; i++) out[n++] = S.sigma[i];
+    return n;
 }
 
 // Octave geometry (w, h, wa per octave) for an input of w x h (PyramidCU.cpp:89-271).

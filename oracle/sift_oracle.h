@@ -4,13 +4,16 @@
 // linked into libsiftgpu.so and nothing in the product calls it.  Only tests/,
 // __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it (oracle/liboracle.so).
 //
-// Parity status: the reference (CUDA + OpenGL) cannot be compiled or run anywhere in this
-// pipeline (no nvcc, no NVIDIA GPU, GL/glew.h and DevIL absent), and it ships
-// no tests or fixtures.  The restatement is pinned by the known-answer values the reference
-// itself states (sigma schedule SiftGPU.cpp:459-497, octave geometry PyramidCU.cpp:985,
-// histopyramid widths PyramidCU.cpp:346-348/773) and cross-checked against an independent
-// float64 NumPy restatement (tests/ref_numpy.py); everything beyond those pins is
-// "parity unpinned" against the CUDA binary itself.  See DESIGN.md §3.
+// Parity status: the reference application (CUDA + OpenGL) cannot be compiled or run in this
+// pipeline, but its kernels can: where a checkout of the reference is present, oracle/Makefile
+// compiles ProgramCU.cu for the CPU through oracle/cuda_host, and tests/test_ref_kernels.py holds
+// every stage of this restatement to the reference's own code (exact stages equal, float stages
+// within a measured bound; tests/golden/ref_*.npz keep the pin where the reference is absent).
+// Also pinned by the known-answer values the reference itself states (sigma schedule
+// SiftGPU.cpp:459-497, octave geometry PyramidCU.cpp:985, histopyramid widths
+// PyramidCU.cpp:346-348/773) and an independent float64 NumPy restatement (tests/ref_numpy.py).
+// Out of reach: nvcc's FMA choices, CUDA's device libm, the GL and PyramidCU host paths.  See
+// DESIGN.md §6.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -36,6 +39,12 @@ struct LevelResult {
     std::vector<Candidate> candidates; // raster order (histopyramid output, ListGen_Kernel)
     std::vector<float> oriented;       // 4 floats per candidate after ComputeOrientation_Kernel
                                        // (x, y, s, packed-orientation bits or angle)
+    // keep_stages only: the stage inputs and outputs of this level, as the reference holds them
+    float sigma = 0, sigma_step = 0;   // ComputeOrientation's arguments
+    float tdog = 0, tedge = 0;         // ComputeKEY's arguments
+    std::vector<float> dog;            // DoG levels 1+j, 2+j, 3+j (3 x wa x h)
+    std::vector<float> grad;           // float2 gradient of G[1+j] (wa x h x 2)
+    std::vector<float> key;            // ComputeKEY_Kernel's float4 key image (wa x h x 4)
 };
 
 struct Result {
@@ -52,7 +61,8 @@ struct Result {
 // With img_f32 (and img == nullptr) the input is float luminance, row stride `stride` floats
 // (the GL_FLOAT / host-converted path of GLTexInput::SetImageData, GLTexImage.cpp:981-1006).
 Result extract(const uint8_t* img, int w, int h, int stride, const sgpu_options& opt,
-               bool keep_intermediates = true, const float* img_f32 = nullptr);
+               bool keep_intermediates = true, const float* img_f32 = nullptr,
+               bool keep_stages = false);
 
 // Descriptors (and, without orientations, the strongest orientation) of caller-supplied
 // keypoints on image img (SiftGPU::RunSIFT(num, keys, keys_have_orientation)).  Returns the

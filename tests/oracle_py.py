@@ -48,6 +48,17 @@ def lib():
                                            ctypes.c_int, P(SgpuOptions), ctypes.c_void_p,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p]
+        L.oracle_level_stages.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, P(SgpuOptions), ctypes.c_int,
+                                          ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int]
+        vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.oracle_filter_sigmas.argtypes = [ci, vp, ci]
+        L.oracle_stage_filter.argtypes = [vp, ci, ci, cf, cf, vp]
+        L.oracle_stage_dog.argtypes = [vp, vp, ci, ci, vp, vp]
+        L.oracle_stage_key.argtypes = [vp, vp, vp, ci, ci, cf, cf, ci, vp]
+        L.oracle_stage_list.argtypes = [vp, ci, ci, ci, ci, vp, ci]
+        L.oracle_stage_orientation.argtypes = [vp, ci, vp, vp, ci, ci, cf, cf, cf, cf, ci, ci, vp]
+        L.oracle_stage_descriptor.argtypes = [vp, ci, vp, ci, ci, cf, ci, ci, vp]
         L.oracle_match.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_void_p]
@@ -194,6 +205,112 @@ def features_oct(img, opts=None):
     lib().oracle_features_oct(p, w, h, w, ctypes.byref(opts), feat.ctypes.data, lvl.ctypes.data,
                               n.value, ctypes.byref(n))
     return feat[:n.value], lvl[:n.value]
+
+
+def level_stages(img, octave, level, opts=None):
+    """The stage inputs and outputs of one level as the reference holds them: dict with dog
+    [3, h, wa] (DoG levels 1+j..3+j), grad [h, wa, 2], key [h, wa, 4], list [n, 4] int32 (col,
+    row, 0, 0: the per-level list before orientation), oriented [n, 4], sigma, sigma_step, tdog, tedge (ComputeOrientation's and ComputeKEY's arguments)."""
+    opts = opts or default_options()
+    img, p = _img(img)
+    h, w = img.shape
+    dims = np.zeros(3, np.int32)
+    sig = np.zeros(4, np.float32)
+    fn = lib().oracle_level_stages
+    n = fn(p, w, h, w, ctypes.byref(opts), octave, level, dims.ctypes.data, sig.ctypes.data,
+           None, None, None, None, None, 0)
+    assert n >= 0, (octave, level)
+    wa, ho = int(dims[0]), int(dims[1])
+    out = dict(dog=np.zeros((3, ho, wa), np.float32), grad=np.zeros((ho, wa, 2), np.float32),
+               key=np.zeros((ho, wa, 4), np.float32), list=np.zeros((n, 4), np.int32),
+               oriented=np.zeros((n, 4), np.float32))
+    fn(p, w, h, w, ctypes.byref(opts), octave, level, None, None, out["dog"].ctypes.data,
+       out["grad"].ctypes.data, out["key"].ctypes.data, out["list"].ctypes.data,
+       out["oriented"].ctypes.data, n)
+    out.update(sigma=float(sig[0]), sigma_step=float(sig[1]), tdog=float(sig[2]), tedge=float(sig[3]))
+    return out
+
+
+# ---- single stages on caller-supplied float32 arrays (the inputs tests/ref_kernels.py takes) ----
+def _c32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def stage_filter(img, sigma, width_factor=4.0):
+    src = _c32(img)
+    h, w = src.shape
+    dst = np.zeros_like(src)
+    lib().oracle_stage_filter(src.ctypes.data, w, h, sigma, width_factor, dst.ctypes.data)
+    return dst
+
+
+def stage_dog(prev, cur, gradient=False):
+    p, c = _c32(prev), _c32(cur)
+    h, w = c.shape
+    d = np.zeros((h, w), np.float32)
+    g = np.zeros((h, w, 2), np.float32) if gradient else None
+    lib().oracle_stage_dog(p.ctypes.data, c.ctypes.data, w, h, d.ctypes.data,
+                           g.ctypes.data if gradient else None)
+    return d, g
+
+
+def stage_key(dp, dc, dn, tdog, tedge, subpixel=1):
+    dp, dc, dn = _c32(dp), _c32(dc), _c32(dn)
+    h, w = dc.shape
+    k = np.zeros((h, w, 4), np.float32)
+    lib().oracle_stage_key(dp.ctypes.data, dc.ctypes.data, dn.ctypes.data, w, h, tdog, tedge,
+                           subpixel, k.ctypes.data)
+    return k
+
+
+def stage_list(key_img, base=None):
+    """The per-level list of a key image; base = (width, height) of the pyramid's first octave,
+    which sets the histogram pyramid's depth (default: the key image is that octave)."""
+    k = _c32(key_img)
+    h, w, _ = k.shape
+    bw, bh = base or (w, h)
+    n = lib().oracle_stage_list(k.ctypes.data, w, h, bw, bh, None, 0)
+    lst = np.zeros((max(n, 1), 4), np.int32)
+    lib().oracle_stage_list(k.ctypes.data, w, h, bw, bh, lst.ctypes.data, n)
+    return lst[:n]
+
+
+def stage_orientation(lst, key_img, grad, sigma, sigma_step, gaussian_factor=1.5,
+                      window_factor=2.0, num_orientation=2, subpixel=1):
+    lst = np.ascontiguousarray(lst, np.int32)
+    k, g = _c32(key_img), _c32(grad)
+    h, w, _ = g.shape
+    out = np.zeros((len(lst), 4), np.float32)
+    lib().oracle_stage_orientation(lst.ctypes.data, len(lst), k.ctypes.data, g.ctypes.data, w, h,
+                                   sigma, sigma_step, gaussian_factor, window_factor,
+                                   num_orientation, subpixel, out.ctypes.data)
+    return out
+
+
+def stage_descriptor(keys, grad, window_factor=3.0, normalized=1, rect=False):
+    k, g = _c32(keys).reshape(-1, 4), _c32(grad)
+    h, w, _ = g.shape
+    out = np.zeros((len(k), 128), np.float32)
+    lib().oracle_stage_descriptor(k.ctypes.data, len(k), g.ctypes.data, w, h, window_factor,
+                                  normalized, int(rect), out.ctypes.data)
+    return out
+
+
+def filter_sigmas(dog_level_num):
+    """Every non-zero sigma FilterImage runs with at -d dog_level_num (initial smoothing, octave
+    change, level to level)."""
+    buf = np.zeros(32, np.float32)
+    n = lib().oracle_filter_sigmas(dog_level_num, buf.ctypes.data, 32)
+    return [float(v) for v in buf[:n] if v > 0]
+
+
+def hist_widths(wa, h, base=None):
+    """Histogram-pyramid level widths for an octave of wa x h in a pyramid whose first octave is
+    base = (width, height) (default: this octave)."""
+    buf = np.zeros(16, np.int32)
+    bw, bh = base or (wa, h)
+    n = lib().oracle_hist_widths(wa, bw, bh, buf.ctypes.data, 16)
+    return [int(v) for v in buf[:n]]
 
 
 def describe_keys(img, keys, has_orientation=True, opts=None):

@@ -492,17 +492,19 @@ def test_sizes_under_panel_limited_plans(gpu_ctx, mbm, nfill, chunks):
 # ---- 13: exact ties inside one long chunk ---------------------------------------------------------
 
 # Three columns of set 2 that copy one row of set 1 each (planted here; the first tile is the
-# one of the lowest column).  (101, 133, 293): the same col % 32 in three consecutive tiles and
-# three 32-column blocks, so the running maximum changes in its low two bits only and the first
-# tile's winner stays.  (8990, 4101, 37): 37 and 4101 share col % 32 = 5 (8990 % 32 is 30, so that
-# column loses on the first criterion); 37, in the first tile, survives the later equal keys.
-# (8965, 4069, 5): decreasing columns of one col % 32, the lowest in the first tile.
-# (70, 4131, 8801): col % 32 = 6, 3, 1, so a later tile takes over twice -- but these columns
-# belong to three lanes of the fold (a lane owns the columns of one col % 16), whose winners meet
-# only in the final lane merge.  (86, 4102, 8790): col % 32 = 22, 6, 22 with one col % 16, so one
-# lane's recorded winner must move from the first tile to tile 32 on col % 32 alone (the
-# "prefix grows" rule with an equal dot) and stay there in tile 68.
-TIE_TRIPLES = [(101, 133, 293), (8990, 4101, 37), (8965, 4069, 5), (70, 4131, 8801),
+# one of the lowest column).  RowMatch_Kernel ranks a column by col % 32 with its 5 bits reversed
+# (sift_synth.tie_winner), lower first.  (101, 133, 293): the same col % 32 in three consecutive
+# tiles and three 32-column blocks, so the running maximum changes in its low two bits only and
+# the first tile's winner stays.  (8967, 4101, 37): 37 and 4101 share col % 32 = 5, rank 20
+# (8967 % 32 is 7, rank 28, so that column loses on the first criterion); 37, in the first tile,
+# survives the later equal keys.  (8965, 4069, 5): decreasing columns of one col % 32, the lowest
+# in the first tile.  (67, 4129, 8806): col % 32 = 3, 1, 6 with ranks 24, 16, 12, so a later tile
+# takes over twice -- but these columns belong to three lanes of the fold (a lane owns the
+# columns of one col % 16), whose winners meet only in the final lane merge.  (86, 4102, 8790):
+# col % 32 = 22, 6, 22 (ranks 13, 12, 13) with one col % 16, so one lane's recorded winner must
+# move from the first tile to tile 32 on the rank alone (the "prefix grows" rule with an equal
+# dot) and stay there in tile 68.
+TIE_TRIPLES = [(101, 133, 293), (8967, 4101, 37), (8965, 4069, 5), (67, 4129, 8806),
                (86, 4102, 8790)]
 
 
@@ -549,8 +551,8 @@ def test_exact_ties_in_one_long_chunk(gpu_ctx, mbm, nfill):
     # the winners: the oracle's, which follow RowMatch_Kernel's rule for three columns too
     won = dict(map(tuple, tie.tolist()))
     assert [won.get(i) for i in rows] == [tie_winner(x, y) for x, y in TIE_COLS]
-    assert [won.get(i) for i in rows3] == [min(cs, key=lambda c: (c % 32, c)) for cs in TIE_TRIPLES]
-    assert [won.get(i) for i in rows3] == [101, 37, 5, 8801, 4102]
+    assert [won.get(i) for i in rows3] == [tie_winner(*cs) for cs in TIE_TRIPLES]
+    assert [won.get(i) for i in rows3] == [101, 37, 5, 8806, 4102]
     pr = dict(map(tuple, got[1024].tolist()))
     assert [pr.get(i) for i in rows + rows3] == [won[i] for i in rows + rows3]
 

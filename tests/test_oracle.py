@@ -118,13 +118,15 @@ def test_extract_deterministic_and_sane():
 def _np_top(dm, distmax, ratiomax, mod32=False):
     """Row/column decision on a dense value matrix: maximum from (0, -1, 0), second = the largest
     remaining value.  Equal maxima: the first index (ColMatch order), or with mod32 the index
-    lowest mod 32, then lowest (RowMatch_Kernel's 32 strided threads + tree reduction,
-    ProgramCU.cu:1803-1835)."""
+    whose residue mod 32 is lowest with its 5 bits reversed, then lowest (RowMatch_Kernel's 32
+    strided threads + tree reduction, ProgramCU.cu:1803-1835; tests/test_ref_kernels.py runs
+    that kernel itself)."""
     arg = np.argmax(dm, axis=1)
     mx = dm[np.arange(dm.shape[0]), arg]
     if mod32:
         cols = np.arange(dm.shape[1])
-        rank = np.where(dm == mx[:, None], (cols % 32) * dm.shape[1] + cols, np.iinfo(np.int64).max)
+        rev = np.array([int(format(t, "05b")[::-1], 2) for t in range(32)])
+        rank = np.where(dm == mx[:, None], rev[cols % 32] * dm.shape[1] + cols, np.iinfo(np.int64).max)
         arg = np.argmin(rank, axis=1)
     srt = np.sort(dm, axis=1)
     sec = srt[:, -2] if dm.shape[1] > 1 else np.zeros_like(mx)
@@ -275,7 +277,7 @@ def test_matcher_tie_rules(mbm):
     if not mbm:
         pairs = dict(map(tuple, got.tolist()))
         assert [pairs[i] for i in rows] == [tie_winner(a, b) for a, b in TIE_COLS]
-        assert [pairs[i] for i in rows] == [34, 66, 3, 32, 7]
+        assert [pairs[i] for i in rows] == [34, 40, 3, 32, 7]
 
 
 def test_golden_fixtures():
