@@ -553,6 +553,69 @@ int sgpu_debug_gaussian(sgpu_ctx* ctx, int image, int octave, int level, float* 
  * {col, row, level_id, image} ints and {dx, dy, ds, pad} floats.  Returns count via *n. */
 int sgpu_debug_candidates(sgpu_ctx* ctx, int* ints, float* floats, int cap, int* n);
 
+/* Verified matches of many set pairs in one call: putative matching, one H and / or F per pair
+ * with local refinement, and guided matching under those matrices, queued back to back on the
+ * device.  Neither a match nor a matrix crosses PCIe between the stages, and the host validates
+ * and plans once.  No reference counterpart (SiftMatchGPU::GetGuidedSiftMatch takes H and F from
+ * the caller, SiftGPU.h:313-321).
+ *
+ * Contract: the results are the bits of the chain of the separate calls.  Let
+ *   1  P = sgpu_match_batch(desc, ..., distmax, ratiomax, mutual_best_match, max_match) with a
+ *      cap that holds everything;
+ *   2  for each requested model X: sgpu_estimate_batch_refined(loc, ..., matches = P, model X,
+ *      X_threshold, iterations, seed, refine_rounds) -- the same seed for both models, the same
+ *      pair positions;
+ *   3  sgpu_match_batch_guided(desc, loc, ..., H, F, distmax, ratiomax, hdistmax, fdistmax,
+ *      mutual_best_match, max_match, cap).
+ * Then out_putative (or NULL) [npairs] = P's counts; out_H / out_F [npairs][9] and
+ * out_inliers_H / out_inliers_F (or NULL) [npairs] = step 2's bytes; out_pairs, out_counts and
+ * the return value = step 3's, with its cap / SGPU_ERANGE convention (the putative pass has no
+ * cap) and its legal pair lists.  out_H == NULL: no H is estimated and the guided pass runs under
+ * the identity with threshold 1e20 for H, as a NULL H does there; the same for F.  A pair with
+ * fewer putative matches than a requested model's minimal sample, or without a valid hypothesis,
+ * gets a zero matrix and therefore no verified match, exactly as the chain gives.
+ *
+ * desc, loc, set_offsets, set_pairs and flags: as sgpu_match_batch_guided (SGPU_INPUT_DEVICE
+ * covers desc and loc).  SGPU_EINVAL, all checked on the host before anything is queued: every
+ * argument error of the three calls, NULL params, iterations outside [1, 65536], refine_rounds
+ * outside [0, 16], out_H and out_F both NULL (that call is sgpu_match_batch), a NULL loc or desc
+ * with rows to read.
+ * One table upload, at most two synchronisations, and no device-to-host copy or host wait before
+ * the last kernel is queued; the number of launches, copies and synchronisations depends neither
+ * on npairs nor on refine_rounds.  sgpu_last_timing's times[13] is the call's device time, from
+ * before its first kernel to after its last; the call leaves times[8] and times[12] as they were. */
+typedef struct sgpu_verify_params {
+    float distmax, ratiomax;        /* both matching passes (sgpu_match_batch's)            */
+    int   mutual_best_match;
+    int   max_match;                /* per pair, both passes                                */
+    float h_threshold, f_threshold; /* estimator thresholds (sgpu_estimate_batch's)         */
+    float hdistmax, fdistmax;       /* guided pass thresholds (sgpu_match_batch_guided's)   */
+    int   iterations;               /* 1 .. 65536                                           */
+    uint32_t seed;
+    int   refine_rounds;            /* 0 .. 16                                              */
+} sgpu_verify_params;
+/* distmax 0.7, ratiomax 0.8, mutual_best_match 1, max_match 4096; h_threshold 2.0, f_threshold
+ * 4.0; hdistmax 2.0, fdistmax 4.0; iterations 512, seed 0, refine_rounds 3 -- the values this
+ * project's tests and timing scripts run the separate calls with.  Needs no device. */
+void sgpu_default_verify_params(sgpu_verify_params* p);
+int sgpu_verify_batch(sgpu_ctx* ctx, const uint8_t* desc, const float* loc,
+                      const int64_t* set_offsets, int nsets,
+                      const int* set_pairs /* [npairs][2] */, int npairs,
+                      const sgpu_verify_params* params,
+                      float* out_H /* [npairs][9] or NULL */, int* out_inliers_H /* or NULL */,
+                      float* out_F /* [npairs][9] or NULL */, int* out_inliers_F /* or NULL */,
+                      int* out_putative /* [npairs] or NULL */,
+                      int* out_pairs /* [cap][2] */, int64_t cap, int* out_counts /* [npairs] */,
+                      int flags);
+/* sgpu_verify_batch over the last extract: sets, descriptors and locations as
+ * sgpu_match_images_guided takes them (the device u8 descriptors, x, y of the device keys; a
+ * multi-part batch: its gathered buffers).  Error conditions of sgpu_match_images_guided and
+ * sgpu_verify_batch. */
+int sgpu_verify_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
+                       const sgpu_verify_params* params,
+                       float* out_H, int* out_inliers_H, float* out_F, int* out_inliers_F,
+                       int* out_putative, int* out_pairs, int64_t cap, int* out_counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,7 +61,7 @@ struct DevBuf {
 // reference's "Detection" and "Feature List" stages, SiftPyramid.cpp:107,123); T_LIST is the
 // row-scan part of it
 enum { T_UPLOAD, T_PYRAMID, T_DETECT, T_ORIENT, T_EXPAND, T_DESC, T_DOWNLOAD, T_TOTAL, T_MATCH,
-       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_N };
+       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_N };
 
 // One part of a batch: consecutive images [img0, img0 + n) with their own stream and buffers.
 struct Part {
@@ -209,6 +209,11 @@ struct sgpu_ctx {
     sgh::DevBuf e_loc, e_plan, e_pts, e_slots, e_out, e_mask;
     sgeo::Plan e_hplan;
     std::vector<unsigned char> e_tables, e_result;
+    // verify chain (sgpu_verify_batch; the matcher's and the estimator's buffers above carry its
+    // tables, partials, decisions, matches and float4 rows): everything the stages hand each other
+    // on the device and the one block that comes down (layout: sgpu_verify.cpp), its host copy
+    sgh::DevBuf v_buf;
+    std::vector<unsigned char> v_result;
     // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
     // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
     sgh::DevBuf q_in, q_out, f_u8, f_s8, f_sums;

@@ -18,6 +18,9 @@
 //   k_estimate_refine   (sgpu_estimate_*_refined, rounds > 0) a 64-lane workgroup per pair: the
 //                       contract's round loop -- least-squares refit on the inliers, rescoring,
 //                       acceptance -- inside one launch, whatever the number of rounds.
+// The verify chain (sgpu_verify_batch) feeds these from the matcher's device
+// output: k_verify_pair_recs, k_verify_gather, k_estimate_pairs<MODEL, true> and
+// k_verify_guided_params, at the end of this file's kernels.
 #include "sift_kernels.h"
 #include "sift_geom.h"
 
@@ -27,15 +30,11 @@ namespace {
 constexpr int kThreads = sgeo::kBlockHyp;
 static_assert(kThreads == 256 && sgeo::kMatchTile % kThreads == 0, "a lane per hypothesis");
 
-__global__ __launch_bounds__(256) void k_estimate_gather(const float* __restrict__ loc,
-                                                         int loc_stride,
-                                                         const sgeo::PairRec* __restrict__ pairs,
-                                                         int npairs,
-                                                         const int* __restrict__ matches,
-                                                         long long total,
-                                                         float4* __restrict__ pts) {
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= total) return;
+// match k of the concatenated list -> its float4 row
+__device__ __forceinline__ void gather_row(const float* __restrict__ loc, int loc_stride,
+                                           const sgeo::PairRec* __restrict__ pairs, int npairs,
+                                           const int* __restrict__ matches, long long k,
+                                           float4* __restrict__ pts) {
     // the last pair whose first match is <= k (pairs without matches share their successor's)
     int lo = 0, hi = npairs - 1;
     while (lo < hi) {
@@ -50,7 +49,22 @@ __global__ __launch_bounds__(256) void k_estimate_gather(const float* __restrict
     pts[k] = make_float4(a.x, a.y, b.x, b.y);
 }
 
-template <int MODEL>
+__global__ __launch_bounds__(256) void k_estimate_gather(const float* __restrict__ loc,
+                                                         int loc_stride,
+                                                         const sgeo::PairRec* __restrict__ pairs,
+                                                         int npairs,
+                                                         const int* __restrict__ matches,
+                                                         long long total,
+                                                         float4* __restrict__ pts) {
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= total) return;
+    gather_row(loc, loc_stride, pairs, npairs, matches, k, pts);
+}
+
+// GUARD (the verify chain, whose items the host makes for every pair): a work item of a pair
+// below the minimal sample ends here, the whole workgroup at once (pr is the workgroup's), before
+// any barrier and before sample() could draw from fewer than S matches; its slot stays 0.
+template <int MODEL, bool GUARD = false>
 __global__ __launch_bounds__(256) void k_estimate_pairs(const float4* __restrict__ pts,
                                                         const sgeo::PairRec* __restrict__ pairs,
                                                         const sgeo::Item* __restrict__ items,
@@ -61,6 +75,7 @@ __global__ __launch_bounds__(256) void k_estimate_pairs(const float4* __restrict
     __shared__ unsigned long long s_best[kThreads / 64];
     const sgeo::Item it = items[blockIdx.x];
     const sgeo::PairRec pr = pairs[it.pair];
+    if (GUARD && pr.m < (MODEL == sgeo::kModelF ? 8 : 4)) return;
     const float4* __restrict__ P = pts + pr.moff;
     const int m = pr.m;
     const uint32_t t = (uint32_t)it.block * kThreads + threadIdx.x;
@@ -315,7 +330,90 @@ __global__ __launch_bounds__(64) void k_estimate_refine(const float4* __restrict
         }
 }
 
+// ---- the verify chain's glue: the matcher's device output -> the estimator's tables -> the
+// guided matcher's matrices, nothing through the host
+
+__global__ __launch_bounds__(256) void k_verify_pair_recs(const long long* __restrict__ offs,
+                                                          const int* __restrict__ counts, int npairs,
+                                                          sgeo::PairRec* __restrict__ recs) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npairs) return;
+    recs[p].moff = offs[p];
+    recs[p].m = counts[p];
+}
+
+// k_estimate_gather under a total that only the device knows: the grid covers the host's bound
+__global__ __launch_bounds__(256) void k_verify_gather(const float* __restrict__ loc, int loc_stride,
+                                                       const sgeo::PairRec* __restrict__ pairs,
+                                                       int npairs, const int* __restrict__ matches,
+                                                       const long long* __restrict__ total,
+                                                       float4* __restrict__ pts) {
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= *total) return;
+    gather_row(loc, loc_stride, pairs, npairs, matches, k, pts);
+}
+
+__global__ __launch_bounds__(256) void k_verify_guided_params(const float* __restrict__ H,
+                                                              const float* __restrict__ F,
+                                                              float hdistmax, float fdistmax,
+                                                              int npairs,
+                                                              GuidedParams* __restrict__ geom) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npairs) return;
+    GuidedParams g;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const float id = i % 4 == 0 ? 1.f : 0.f;
+        g.H[i] = H ? H[9 * (size_t)p + i] : id;
+        g.F[i] = F ? F[9 * (size_t)p + i] : id;
+    }
+    g.hdistmax = H ? hdistmax : 1.0e+20f;
+    g.fdistmax = F ? fdistmax : 1.0e+20f;
+    geom[p] = g;
+}
+
 }  // namespace
+
+hipError_t launch_verify_pair_recs(const long long* offs, const int* counts, int npairs,
+                                   sgeo::PairRec* recs, hipStream_t stream) {
+    if (npairs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_verify_pair_recs, dim3((npairs + 255) / 256), dim3(256), 0, stream, offs,
+                       counts, npairs, recs);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify_gather(const float* loc, int loc_stride, const sgeo::PairRec* pairs,
+                                int npairs, const int* matches, const long long* total,
+                                long long bound, float4* pts, hipStream_t stream) {
+    if (bound <= 0 || npairs <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)((bound + 255) / 256);
+    hipLaunchKernelGGL(k_verify_gather, dim3(grid), dim3(256), 0, stream, loc, loc_stride, pairs,
+                       npairs, matches, total, pts);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify_estimate_pairs(const float4* pts, const sgeo::PairRec* pairs,
+                                        const sgeo::Item* items, int nitems, int model,
+                                        float threshold, int iterations, uint32_t seed,
+                                        unsigned long long* slots, hipStream_t stream) {
+    if (nitems <= 0) return hipSuccess;
+    if (model == sgeo::kModelF)
+        hipLaunchKernelGGL((k_estimate_pairs<sgeo::kModelF, true>), dim3(nitems), dim3(kThreads), 0,
+                           stream, pts, pairs, items, threshold, iterations, seed, slots);
+    else
+        hipLaunchKernelGGL((k_estimate_pairs<sgeo::kModelH, true>), dim3(nitems), dim3(kThreads), 0,
+                           stream, pts, pairs, items, threshold, iterations, seed, slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify_guided_params(const float* H, const float* F, float hdistmax,
+                                       float fdistmax, int npairs, GuidedParams* geom,
+                                       hipStream_t stream) {
+    if (npairs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_verify_guided_params, dim3((npairs + 255) / 256), dim3(256), 0, stream, H,
+                       F, hdistmax, fdistmax, npairs, geom);
+    return hipGetLastError();
+}
 
 hipError_t launch_estimate_refine(const float4* pts, const sgeo::PairRec* pairs, int npairs,
                                   int model, float threshold, int rounds, float* models,

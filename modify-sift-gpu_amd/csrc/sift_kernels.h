@@ -498,4 +498,26 @@ hipError_t launch_estimate_finish(const float4* pts, const sgeo::PairRec* pairs,
 hipError_t launch_estimate_refine(const float4* pts, const sgeo::PairRec* pairs, int npairs,
                                   int model, float threshold, int rounds, float* models,
                                   int* inliers, uint8_t* mask, int* rounds_done, hipStream_t stream);
+
+// ---- the verify chain's device-side glue (sift_geom.hip; sgpu_verify_batch) ----
+// A thread per pair: recs[p].moff = offs[p], recs[p].m = counts[p], from the compaction's device
+// offsets and counts (a_off / b_off come from the host's upload).
+hipError_t launch_verify_pair_recs(const long long* offs, const int* counts, int npairs,
+                                   sgeo::PairRec* recs, hipStream_t stream);
+// launch_estimate_gather whose total is on the device: the grid covers `bound` matches and every
+// thread compares its index with *total (bound >= *total).
+hipError_t launch_verify_gather(const float* loc, int loc_stride, const sgeo::PairRec* pairs,
+                                int npairs, const int* matches, const long long* total,
+                                long long bound, float4* pts, hipStream_t stream);
+// launch_estimate_pairs over items that the host made without knowing the match counts: a work
+// item of a pair below the model's minimal sample ends before it samples and writes nothing.
+hipError_t launch_verify_estimate_pairs(const float4* pts, const sgeo::PairRec* pairs,
+                                        const sgeo::Item* items, int nitems, int model,
+                                        float threshold, int iterations, uint32_t seed,
+                                        unsigned long long* slots, hipStream_t stream);
+// A thread per pair: geom[p] from the device models H / F [npairs][9]; a null array is the
+// identity with its threshold at 1e20, the bytes sgpu_match_batch_guided builds on the host.
+hipError_t launch_verify_guided_params(const float* H, const float* F, float hdistmax,
+                                       float fdistmax, int npairs, GuidedParams* geom,
+                                       hipStream_t stream);
 }  // namespace sgk

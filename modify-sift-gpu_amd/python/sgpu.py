@@ -11,7 +11,7 @@ import subprocess
 
 import numpy as np
 
-from sgpu_types import SgpuOptions, default_options
+from sgpu_types import SgpuOptions, SgpuVerifyParams, default_options
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # SGPU_LIB_PATH: an experiment build of the same library (tests/build_variant.sh); default: the
@@ -40,6 +40,7 @@ C_API = [
     "sgpu_match_batch_guided", "sgpu_match_images_guided",
     "sgpu_estimate_batch", "sgpu_estimate_images",
     "sgpu_estimate_batch_refined", "sgpu_estimate_images_refined",
+    "sgpu_default_verify_params", "sgpu_verify_batch", "sgpu_verify_images",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -135,6 +136,12 @@ def lib():
                                                   c.c_int, vp, vp, vp, vp, c.c_int]
         L.sgpu_estimate_images_refined.argtypes = [vp, vp, c.c_int, vp, vp, c.c_int, c.c_float,
                                                    c.c_int, c.c_uint32, c.c_int, vp, vp, vp, vp]
+        L.sgpu_default_verify_params.argtypes = [P(SgpuVerifyParams)]
+        L.sgpu_default_verify_params.restype = None
+        L.sgpu_verify_batch.argtypes = [vp, vp, vp, vp, c.c_int, vp, c.c_int, P(SgpuVerifyParams),
+                                        vp, vp, vp, vp, vp, vp, c.c_int64, vp, c.c_int]
+        L.sgpu_verify_images.argtypes = [vp, vp, c.c_int, P(SgpuVerifyParams), vp, vp, vp, vp, vp,
+                                         vp, c.c_int64, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -753,6 +760,103 @@ class SiftContext:
             return lib().sgpu_estimate_images(self._ctx, pr, npairs, cat, counts, mdl, thr, it, sd,
                                               models, inliers, mask)
         return self._estimate(call, pairs, matches, model, threshold, iterations, seed)
+
+    @staticmethod
+    def verify_params(**params) -> SgpuVerifyParams:
+        """sgpu_default_verify_params with the given fields of sgpu_verify_params replaced."""
+        vp = SgpuVerifyParams()
+        lib().sgpu_default_verify_params(ctypes.byref(vp))
+        names = {f[0] for f in SgpuVerifyParams._fields_}
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError(f"unknown verify parameter {k!r}")
+            setattr(vp, k, int(v) & 0xFFFFFFFF if k == "seed" else v)
+        return vp
+
+    def _verify(self, call, pairs, sizes, H, F, cap, params):
+        """Common part of verify_batch / verify_images: call(pairs pointer, npairs, params, the
+        five model outputs' pointers, out, cap, counts) -> the C return value."""
+        if not H and not F:
+            raise ValueError("verify needs a model: H, F or both (match_batch matches without one)")
+        vp = self.verify_params(**params)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        npairs = len(pr)
+        if cap is None:
+            ok = (pr >= 0).all() and (pr < len(sizes)).all()
+            cap = int(sum(min(int(sizes[a]), vp.max_match) for a in pr[:, 0])) if ok and vp.max_match > 0 else 0
+        cap = int(cap)
+        out = np.zeros((max(cap, 1), 2), np.int32)
+        counts = np.zeros(max(npairs, 1), np.int32)
+        putative = np.zeros(max(npairs, 1), np.int32)
+        models = [np.zeros((max(npairs, 1), 9), np.float32) if want else None for want in (H, F)]
+        inliers = [np.zeros(max(npairs, 1), np.int32) if want else None for want in (H, F)]
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = call(pr.ctypes.data if npairs else None, npairs, ctypes.byref(vp), ptr(models[0]),
+                  ptr(inliers[0]), ptr(models[1]), ptr(inliers[1]), putative.ctypes.data,
+                  out.ctypes.data, cap, counts.ctypes.data)
+        if rc < 0 and rc != SGPU_ERANGE:
+            self._check(rc, "verify")
+        counts = counts[:npairs]
+        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        res = [out[offs[p]:offs[p + 1]].copy() for p in range(npairs) if offs[p + 1] <= cap]
+        ms = [None if m is None else m[:npairs].reshape(npairs, 3, 3).copy() for m in models]
+        ins = [None if i is None else i[:npairs].copy() for i in inliers]
+        rest = (ms[0], ins[0], ms[1], ins[1], putative[:npairs].copy())
+        if rc == SGPU_ERANGE:
+            e = MatchOverflow(counts.copy(), res)
+            e.verified = rest
+            raise e
+        return (res,) + rest
+
+    def verify_batch(self, desc_u8, loc, offsets, pairs, H=True, F=False, cap=None,
+                     device_ptrs=None, **params):
+        """Verified matches of many set pairs in one call (sgpu_verify_batch): match_batch, then
+        estimate_batch_refined for H and / or F, then match_batch_guided under those models, all on
+        the device -- the bits of that chain.  desc_u8 [rows][128], loc [rows][2], offsets and
+        pairs as match_batch_guided; params: fields of sgpu_verify_params (verify_params()).
+        Returns (one [m, 2] int32 array per pair, H [npairs][3][3], inliers_H [npairs], F,
+        inliers_F, putative counts [npairs]), None for a model not asked for; more verified matches
+        than cap raise MatchOverflow (its .verified = the other five).  device_ptrs = (descriptors,
+        locations): int device addresses read in place (SGPU_INPUT_DEVICE; desc_u8, loc ignored)."""
+        off = np.ascontiguousarray(offsets, np.int64)
+        nsets = len(off) - 1
+        if device_ptrs is not None:
+            dp, lp = (ctypes.c_void_p(a) for a in device_ptrs)
+            flags = SGPU_INPUT_DEVICE
+            if nsets < 0:
+                raise ValueError("offsets must hold at least one entry")
+        else:
+            d = np.ascontiguousarray(desc_u8, np.uint8).reshape(-1, 128)
+            lc = np.ascontiguousarray(loc, np.float32)
+            if lc.ndim != 2 or lc.shape != (len(d), 2):
+                raise ValueError(f"locations must be [rows][2] for {len(d)} rows, got {lc.shape}")
+            if nsets < 0 or (len(off) and off[-1] > len(d)):
+                raise ValueError("offsets do not fit the descriptor buffer")
+            dp, lp = (d.ctypes.data if len(d) else None), (lc.ctypes.data if len(lc) else None)
+            flags = SGPU_INPUT_HOST
+
+        def call(pr, npairs, vp, *outs):
+            return lib().sgpu_verify_batch(self._ctx, dp, lp, off.ctypes.data, nsets, pr, npairs, vp,
+                                           *outs, flags)
+        return self._verify(call, pairs, np.diff(off), H, F, cap, params)
+
+    def verify_images(self, pairs, H=True, F=False, cap=None, **params):
+        """verify_batch over the last extract (sgpu_verify_images): descriptors and locations as
+        match_images_guided takes them; nothing of them leaves HBM."""
+        if not H and not F:
+            raise ValueError("verify needs a model: H, F or both (match_images matches without one)")
+        sizes = np.array([self.count(i) for i in range(self.batch)], np.int64)
+
+        def call(pr, npairs, vp, *outs):
+            return lib().sgpu_verify_images(self._ctx, pr, npairs, vp, *outs)
+        return self._verify(call, pairs, sizes, H, F, cap, params)
+
+    def verify_time(self) -> float:
+        """Device milliseconds of the last verify_batch / verify_images (sgpu_last_timing's
+        times[13]); timing() keeps the slots it has always returned."""
+        t = np.zeros(14, np.float32)
+        lib().sgpu_last_timing(self._ctx, t.ctypes.data, 14)
+        return float(t[13])
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,

@@ -32,6 +32,23 @@ class SgpuOptions(ctypes.Structure):
     ]
 
 
+class SgpuVerifyParams(ctypes.Structure):
+    """ctypes mirror of `sgpu_verify_params` (sgpu_verify_batch)."""
+    _fields_ = [
+        ("distmax", ctypes.c_float),
+        ("ratiomax", ctypes.c_float),
+        ("mutual_best_match", ctypes.c_int),
+        ("max_match", ctypes.c_int),
+        ("h_threshold", ctypes.c_float),
+        ("f_threshold", ctypes.c_float),
+        ("hdistmax", ctypes.c_float),
+        ("fdistmax", ctypes.c_float),
+        ("iterations", ctypes.c_int),
+        ("seed", ctypes.c_uint32),
+        ("refine_rounds", ctypes.c_int),
+    ]
+
+
 def default_options(**kw) -> SgpuOptions:
     o = SgpuOptions(filter_width_factor=4.0, descriptor_window_factor=3.0,
                     orientation_window_factor=2.0, orientation_gaussian_factor=1.5,
