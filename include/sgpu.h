@@ -385,7 +385,8 @@ int sgpu_estimate_images_refined(sgpu_ctx* ctx, const int* image_pairs, int npai
  * {upload, pyramid, detect, orientation, expand, descriptor, download, total} of the last
  * extract; times[8] = the last sgpu_match call; times[9] = the feature-list (row scan) part of
  * detect; times[10], [11] = the key and descriptor copies of the last sgpu_copy_features;
- * times[12] = the last sgpu_estimate_* call.
+ * times[12] = the last sgpu_estimate_* call; times[13] = the last sgpu_verify_* call; times[14] =
+ * the last sgpu_prematch_* call.
  * SiftGPU::_timing[2..8] map them to the reference's slots (siftgpu_api.cpp).  Slots 0-7 and
  * 9-11 read 0 after a one-stream extract / copy made with the stage timing off. */
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n);
@@ -615,6 +616,58 @@ int sgpu_verify_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
                        const sgpu_verify_params* params,
                        float* out_H, int* out_inliers_H, float* out_F, int* out_inliers_F,
                        int* out_putative, int* out_pairs, int64_t cap, int* out_counts);
+
+/* Preemptive matching: which pairs of a batch are worth matching, from every set's `top`
+ * largest-scale rows alone (Wu, "Towards Linear-time Incremental Structure from Motion", 3DV 2013,
+ * section 3: h = 100 features, pairs with at least 4 subset matches are kept).  No reference
+ * counterpart in SiftMatchGPU.  The selection, the gather of the selected rows and the matching of
+ * the subsets run on the device; the thresholding of the counts is the caller's.
+ *
+ * Selection rule (csrc/sift_select.h): of a set of n rows, m = min(n, top) are
+ * selected: the rows with the largest scales, compared as the monotone unsigned image of their
+ * float bits (a total order of every bit pattern; the numeric order for the positive finite scales
+ * of extracted keys), equal values resolving to the lower row index.  The selection is reported as
+ * set-local row indices in ascending order.
+ *
+ * sgpu_select_top_scale_batch: the scale of buffer row r is scale[r * scale_stride] (host memory,
+ * or device memory with SGPU_INPUT_DEVICE; the floats up to the last row's scale are read), set s =
+ * rows [set_offsets[s], set_offsets[s + 1]).  out_offsets[0 .. nsets] = the scan of min(n_s, top),
+ * out_index[out_offsets[s] ..) = set s's selection.  sgpu_select_top_scale_images: the sets are the
+ * last extract's images, the scale column 2 of its device keys. */
+int sgpu_select_top_scale_batch(sgpu_ctx* ctx, const float* scale, int scale_stride /* floats */,
+                                const int64_t* set_offsets, int nsets, int top,
+                                int* out_index /* [sum min(n_s, top)] */,
+                                int64_t* out_offsets /* [nsets + 1] */, int flags);
+int sgpu_select_top_scale_images(sgpu_ctx* ctx, int top, int* out_index, int64_t* out_offsets);
+/* sgpu_prematch_batch -- contract: the bits of the chain.  With idx_s the selection of set s, pair
+ * (a, b) gives exactly sgpu_match_batch on the two gathered subsets (rows idx_a and idx_b, in that
+ * ascending order) with max_match = top, and every match {i, j} is reported as {idx_a[i],
+ * idx_b[j]}: set-local rows, still in ascending first index.  top >= every n returns the bits of
+ * sgpu_match_batch with max_match = top.
+ * desc, set_offsets and the legal pair lists are sgpu_match_batch's (a device desc is 16-byte
+ * aligned); scale as above, host or device memory together with desc.  set_pairs == NULL: all pairs
+ * a < b in lexicographic order, and npairs must be nsets (nsets - 1) / 2.  out_counts [npairs] is
+ * always complete and the return value is its total.  out_pairs == NULL: counts only, cap is
+ * ignored and no match is downloaded; otherwise sgpu_match_batch's cap / SGPU_ERANGE convention.
+ * SGPU_EINVAL, checked on the host before anything is queued: top < 1, scale_stride < 1, a NULL
+ * scale or desc with rows to read, NULL out_counts (NULL out_index / out_offsets for the select
+ * calls), bad offsets or pair indices, the all-pairs count mismatch.
+ * The number of launches, copies and synchronisations depends neither on nsets nor on npairs (one
+ * table upload; the host plans from set_offsets and top alone).  sgpu_last_timing's times[14] is
+ * the call's device time, from before the selection to after the last kernel; every other slot is
+ * left as it was.
+ * The _images forms run over the last extract (scales: column 2 of the device keys; descriptors:
+ * the matcher's forms behind sgpu_feature_descriptors_u8, gathered in place of a new preparation;
+ * a multi-part batch: its gathered buffers), with the error conditions of sgpu_match_images. */
+int sgpu_prematch_batch(sgpu_ctx* ctx, const uint8_t* desc, const float* scale, int scale_stride,
+                        const int64_t* set_offsets, int nsets,
+                        const int* set_pairs /* [npairs][2] or NULL */, int npairs, int top,
+                        float distmax, float ratiomax, int mutual_best_match,
+                        int* out_counts /* [npairs] */,
+                        int* out_pairs /* [cap][2] or NULL */, int64_t cap, int flags);
+int sgpu_prematch_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, int top,
+                         float distmax, float ratiomax, int mutual_best_match,
+                         int* out_counts, int* out_pairs, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #include "sift_match_plan.h"
 #include "sift_params.h"
 #include "sift_pyramid_plan.h"
+#include "sift_select.h"
 
 // RCCL's communicator handle as rccl.h declares it (sgpu_comm.cpp alone includes rccl.h)
 typedef struct ncclComm* ncclComm_t;
@@ -61,7 +62,7 @@ struct DevBuf {
 // reference's "Detection" and "Feature List" stages, SiftPyramid.cpp:107,123); T_LIST is the
 // row-scan part of it
 enum { T_UPLOAD, T_PYRAMID, T_DETECT, T_ORIENT, T_EXPAND, T_DESC, T_DOWNLOAD, T_TOTAL, T_MATCH,
-       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_N };
+       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_PREMATCH, T_N };
 
 // One part of a batch: consecutive images [img0, img0 + n) with their own stream and buffers.
 struct Part {
@@ -214,6 +215,14 @@ struct sgpu_ctx {
     // on the device and the one block that comes down (layout: sgpu_verify.cpp), its host copy
     sgh::DevBuf v_buf;
     std::vector<unsigned char> v_result;
+    // preemptive matching (sgpu_prematch_batch, sgpu_select_top_scale_batch; the matcher's b_*
+    // buffers above carry its tables, the subsets' matcher forms, partials, decisions and matches):
+    // uploaded scales, the selected rows' indices, the gathered u8 rows of a caller's descriptors;
+    // its plan over the subset offsets, those offsets and the all-pairs list
+    sgh::DevBuf p_scale, p_index, p_u8;
+    sgplan::Plan p_hplan;
+    std::vector<int64_t> p_sub;
+    std::vector<int> p_pairs;
     // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
     // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
     sgh::DevBuf q_in, q_out, f_u8, f_s8, f_sums;

@@ -520,4 +520,23 @@ hipError_t launch_verify_estimate_pairs(const float4* pts, const sgeo::PairRec* 
 hipError_t launch_verify_guided_params(const float* H, const float* F, float hdistmax,
                                        float fdistmax, int npairs, GuidedParams* geom,
                                        hipStream_t stream);
+
+// ---- preemptive matching (sift_select.hip; sgpu_prematch_batch) ----
+// One workgroup per set: index[sub_off[s] + k] = the k-th of set s's min(n_s, top) largest-scale
+// rows (set-local, ascending; the rule of sift_select.h).  The scale of buffer row r is
+// scale[r * stride]; set s = rows [set_off[s], set_off[s + 1]); sub_off = the scan of min(n_s, top).
+hipError_t launch_select_top_scale(const float* scale, int stride, const long long* set_off,
+                                   const int* sub_off, int nsets, int top, int* index,
+                                   hipStream_t stream);
+// dst row sub_off[s] + k = src row set_off[s] + index[sub_off[s] + k], 128 bytes each (both
+// 16-byte aligned), and dst_terms / src_terms (one int per row) the same way unless dst_terms is
+// null.
+hipError_t launch_gather_rows(const uint8_t* src, const int* src_terms, const long long* set_off,
+                              const int* sub_off, const int* index, int nsets, uint8_t* dst,
+                              int* dst_terms, hipStream_t stream);
+// The matches {i, j} that launch_match_pairs_compact wrote below cap, from subset positions to set
+// rows: {index[pair_sub[2 p] + i], index[pair_sub[2 p + 1] + j]}.
+hipError_t launch_remap_matches(const int* counts, const long long* offs, const int* pair_sub,
+                                const int* index, int npairs, long long cap, int* out,
+                                hipStream_t stream);
 }  // namespace sgk

@@ -41,6 +41,8 @@ C_API = [
     "sgpu_estimate_batch", "sgpu_estimate_images",
     "sgpu_estimate_batch_refined", "sgpu_estimate_images_refined",
     "sgpu_default_verify_params", "sgpu_verify_batch", "sgpu_verify_images",
+    "sgpu_select_top_scale_batch", "sgpu_select_top_scale_images",
+    "sgpu_prematch_batch", "sgpu_prematch_images",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -142,6 +144,13 @@ def lib():
                                         vp, vp, vp, vp, vp, vp, c.c_int64, vp, c.c_int]
         L.sgpu_verify_images.argtypes = [vp, vp, c.c_int, P(SgpuVerifyParams), vp, vp, vp, vp, vp,
                                          vp, c.c_int64, vp]
+        L.sgpu_select_top_scale_batch.argtypes = [vp, vp, c.c_int, vp, c.c_int, c.c_int, vp, vp,
+                                                  c.c_int]
+        L.sgpu_select_top_scale_images.argtypes = [vp, c.c_int, vp, vp]
+        L.sgpu_prematch_batch.argtypes = [vp, vp, vp, c.c_int, vp, c.c_int, vp, c.c_int, c.c_int,
+                                          c.c_float, c.c_float, c.c_int, vp, vp, c.c_int64, c.c_int]
+        L.sgpu_prematch_images.argtypes = [vp, vp, c.c_int, c.c_int, c.c_float, c.c_float, c.c_int,
+                                           vp, vp, c.c_int64]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -857,6 +866,151 @@ class SiftContext:
         t = np.zeros(14, np.float32)
         lib().sgpu_last_timing(self._ctx, t.ctypes.data, 14)
         return float(t[13])
+
+    # ---- preemptive matching (sgpu_select_top_scale_*, sgpu_prematch_*)
+    @staticmethod
+    def _set_offsets(offsets):
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets must hold at least one entry")
+        return off, len(off) - 1
+
+    @staticmethod
+    def _scales(scale, off, stride):
+        """The host scales of select_top_scale / prematch_batch: a flat float32 buffer in which
+        row r's scale is element r * stride."""
+        sc = np.ascontiguousarray(scale, np.float32).reshape(-1)
+        stride = int(stride)
+        rows = int(off[-1])
+        if stride < 1 or (rows > 0 and len(sc) < (rows - 1) * stride + 1):
+            raise ValueError(f"{len(sc)} floats do not hold {rows} scales {stride} apart")
+        return sc, stride
+
+    @staticmethod
+    def _split(flat, offs):
+        return [flat[offs[s]:offs[s + 1]].copy() for s in range(len(offs) - 1)]
+
+    def select_top_scale(self, scale, offsets, top, stride=1, device_ptr=None):
+        """Each set's min(n, top) largest-scale rows (sgpu_select_top_scale_batch; the rule of
+        csrc/sift_select.h: equal scales resolve to the lower row): one ascending int32 array of
+        set-local row indices per set.  scale: flat float32 buffer, row r's scale at r * stride;
+        offsets as match_batch.  device_ptr: the int device address of the scales, read in place
+        (SGPU_INPUT_DEVICE; scale is ignored)."""
+        off, nsets = self._set_offsets(offsets)
+        if device_ptr is not None:
+            ptr, flags, stride = ctypes.c_void_p(device_ptr), SGPU_INPUT_DEVICE, int(stride)
+        else:
+            sc, stride = self._scales(scale, off, stride)
+            ptr, flags = (sc.ctypes.data if len(sc) else None), SGPU_INPUT_HOST
+        sizes = np.diff(off)
+        cap = int(np.minimum(sizes, max(int(top), 0)).clip(0).sum()) if (sizes >= 0).all() else 0
+        index = np.zeros(max(cap, 1), np.int32)
+        sub = np.zeros(nsets + 1, np.int64)
+        self._check(lib().sgpu_select_top_scale_batch(self._ctx, ptr, stride, off.ctypes.data, nsets,
+                                                      int(top), index.ctypes.data, sub.ctypes.data,
+                                                      flags), "sgpu_select_top_scale_batch")
+        return self._split(index, sub)
+
+    def select_top_scale_images(self, top):
+        """select_top_scale over the last extract (sgpu_select_top_scale_images): the scales are
+        column 2 of the batch's device keys."""
+        cap = sum(min(self.count(i), max(int(top), 0)) for i in range(self.batch))
+        index = np.zeros(max(cap, 1), np.int32)
+        sub = np.zeros(self.batch + 1, np.int64)
+        self._check(lib().sgpu_select_top_scale_images(self._ctx, int(top), index.ctypes.data,
+                                                       sub.ctypes.data), "sgpu_select_top_scale_images")
+        return self._split(index, sub)
+
+    def _prematch(self, call, pairs, sizes, top, matches, cap):
+        """Common part of prematch_batch / prematch_images: call(pairs pointer or None, npairs,
+        counts, out or None, cap) -> the C return value."""
+        nsets, top = len(sizes), int(top)
+        if pairs is None:   # all pairs a < b: the library builds the list
+            a, b = np.triu_indices(nsets, 1)
+            first, npairs, ptr = a, len(a), None
+        else:
+            pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+            npairs = len(pr)
+            first = pr[:, 0]
+            # (an empty explicit list is not the all-pairs request: never a null pointer)
+            keep = pr if npairs else np.zeros((1, 2), np.int32)
+            ptr = keep.ctypes.data
+        counts = np.zeros(max(npairs, 1), np.int32)
+        out = None
+        if matches:
+            if cap is None:
+                ok = npairs == 0 or ((first >= 0).all() and (first < nsets).all())
+                cap = int(np.minimum(np.asarray(sizes)[first], top).sum()) if ok and npairs and top > 0 else 0
+            cap = int(cap)
+            out = np.zeros((max(cap, 1), 2), np.int32)
+        rc = call(ptr, npairs, counts.ctypes.data, None if out is None else out.ctypes.data,
+                  cap if matches else 0)
+        counts = counts[:npairs]
+        if rc < 0 and rc != SGPU_ERANGE:
+            self._check(rc, "prematch")
+        if not matches:
+            return counts.copy(), None
+        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        res = [out[offs[p]:offs[p + 1]].copy() for p in range(npairs) if offs[p + 1] <= cap]
+        if rc == SGPU_ERANGE:
+            raise MatchOverflow(counts.copy(), res)
+        return counts.copy(), res
+
+    def prematch_batch(self, desc_u8, scale, offsets, pairs=None, top=100, distmax=0.7, ratiomax=0.8,
+                       mbm=1, matches=True, cap=None, stride=1, device_ptrs=None):
+        """Preemptive matching (sgpu_prematch_batch): every set's `top` largest-scale rows are
+        selected and gathered on the device and the pairs matched on those subsets alone -- the bits
+        of match_batch on the gathered subsets with max_match = top, each match reported in the
+        sets' own row indices.  desc_u8, offsets, pairs as match_batch (pairs=None: all pairs
+        a < b in lexicographic order); scale, stride as select_top_scale.  Returns (counts [npairs]
+        int32, one [m, 2] int32 array per pair, or None with matches=False: counts only, nothing
+        else comes down).  More matches than cap raise MatchOverflow.  device_ptrs = (descriptors,
+        scales): int device addresses read in place (SGPU_INPUT_DEVICE)."""
+        off, nsets = self._set_offsets(offsets)
+        if device_ptrs is not None:
+            dp, sp = (ctypes.c_void_p(a) for a in device_ptrs)
+            flags, stride = SGPU_INPUT_DEVICE, int(stride)
+        else:
+            d = np.ascontiguousarray(desc_u8, np.uint8).reshape(-1, 128)
+            if off[-1] > len(d):
+                raise ValueError("offsets do not fit the descriptor buffer")
+            sc, stride = self._scales(scale, off, stride)
+            dp, sp = (d.ctypes.data if len(d) else None), (sc.ctypes.data if len(sc) else None)
+            flags = SGPU_INPUT_HOST
+
+        def call(pr, npairs, counts, out, cp):
+            return lib().sgpu_prematch_batch(self._ctx, dp, sp, stride, off.ctypes.data, nsets, pr,
+                                             npairs, int(top), distmax, ratiomax, mbm, counts, out,
+                                             cp, flags)
+        return self._prematch(call, pairs, np.diff(off), top, matches, cap)
+
+    def prematch_images(self, pairs=None, top=100, distmax=0.7, ratiomax=0.8, mbm=1, matches=True,
+                        cap=None):
+        """prematch_batch over the last extract (sgpu_prematch_images): scales and descriptors are
+        the batch's own device buffers; pairs=None: all image pairs a < b."""
+        sizes = np.array([self.count(i) for i in range(self.batch)], np.int64)
+
+        def call(pr, npairs, counts, out, cp):
+            return lib().sgpu_prematch_images(self._ctx, pr, npairs, int(top), distmax, ratiomax, mbm,
+                                              counts, out, cp)
+        return self._prematch(call, pairs, sizes, top, matches, cap)
+
+    def candidate_pairs(self, top=100, min_matches=4, distmax=0.7, ratiomax=0.8, mbm=1):
+        """The image pairs a < b of the last extract worth matching in full: those with at least
+        min_matches matches among their `top` largest-scale features (prematch_images over all
+        pairs, counts only; the threshold is applied here).  Returns (pairs [k][2] int32, their
+        counts [k] int32), in lexicographic order."""
+        counts, _ = self.prematch_images(None, top, distmax, ratiomax, mbm, matches=False)
+        a, b = np.triu_indices(self.batch, 1)
+        keep = counts >= int(min_matches)
+        return np.stack([a[keep], b[keep]], axis=1).astype(np.int32).reshape(-1, 2), counts[keep]
+
+    def prematch_time(self) -> float:
+        """Device milliseconds of the last prematch_batch / prematch_images (sgpu_last_timing's
+        times[14])."""
+        t = np.zeros(15, np.float32)
+        lib().sgpu_last_timing(self._ctx, t.ctypes.data, 15)
+        return float(t[14])
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
