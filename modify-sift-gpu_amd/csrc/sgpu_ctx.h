@@ -199,7 +199,8 @@ struct sgpu_ctx {
     std::vector<int> h_match;
     bool dist_ready = false;
     // grouped pair matcher (sgpu_match_batch): uploaded descriptors and their s8 form / row sums,
-    // the planner's tables, chunk partials, decisions, [counts npairs][offsets npairs + 1], pairs
+    // the planner's tables, chunk partials, decisions, [offsets npairs + 1 (64-bit)][counts npairs],
+    // pairs
     sgh::DevBuf b_desc, b_s8, b_sums, b_plan, b_part, b_dec, b_cnt, b_out;
     sgh::DevBuf b_loc;                          // sgpu_match_batch_guided: uploaded locations [rows][2]
     sgplan::Plan b_hplan;
@@ -272,4 +273,67 @@ int ensure_dist_table(sgpu_ctx* ctx);
 int feature_u8(sgpu_ctx* ctx);
 // sgpu_comm.cpp: destroys the context's communicator, if any
 void comm_release(sgpu_ctx* ctx);
+
+// ---- sgpu_pairs.cpp: what the callers of the grouped pair matcher share ----
+// Where a call's sets come from: the last extract (images), or the caller's desc / loc / scale,
+// host memory (uploaded by resolve_sets) or device memory (device).
+struct SetSource {
+    bool images = false, device = false;
+    const uint8_t* desc = nullptr;
+    const float* loc = nullptr;     // [rows][2]
+    const float* scale = nullptr;   // row r's scale at scale[r * scale_stride]
+    int scale_stride = 1;
+};
+// The sets on the device.  s8 / sums are set where the matcher's forms exist (the last extract's).
+struct DeviceSets {
+    const uint8_t* u8 = nullptr;
+    const uint8_t* s8 = nullptr;
+    const int* sums = nullptr;
+    const float* loc = nullptr;     // x, y of row r at loc[r * loc_stride]
+    int loc_stride = 2;
+    const float* scale = nullptr;
+    int scale_stride = 1;
+    bool timing_started = false;    // ev[1] is recorded: the call had to quantise the batch
+};
+enum { SET_DESC = 1, SET_LOC = 2, SET_SCALE = 4 };
+// `need` (SET_*) of the rows [0, rows) on the device: the batch's buffers (SET_DESC quantises them
+// if need be, after recording ev[1]), uploads into b_desc / b_loc / p_scale, or the caller's
+// device pointers as they are.  Queues on ctx->stream, waits for nothing.
+int resolve_sets(sgpu_ctx* ctx, const SetSource& src, int64_t rows, int need, DeviceSets& sets);
+// the states feature_u8 refuses, before anything is queued: "no extracted batch to <what>"
+int check_batch(sgpu_ctx* ctx, const char* what);
+// sgplan's verdict on the set offsets alone, before any size is taken from them
+int probe_offsets(const int64_t* off, int nsets);
+// a trailer's next 8-byte boundary
+inline size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
+// The plan-sized buffers: b_plan (table_bytes), b_part, b_dec, b_out (out_rows), b_cnt for
+// cnt_pairs pairs (0: the caller keeps its counts elsewhere), b_s8 / b_sums for s8_rows rows (0:
+// the matcher's forms exist).
+int ensure_pair_buffers(sgpu_ctx* ctx, const sgplan::Plan& plan, size_t table_bytes,
+                        int64_t out_rows, int cnt_pairs, int64_t s8_rows);
+// s8 / sums of sets.u8's rows into b_s8 / b_sums, one launch, if sets has none
+int derive_s8(sgpu_ctx* ctx, DeviceSets& sets, int64_t rows);
+// One pass of the matcher over a plan's tables: k_match_pairs (guided: loc and geom set), finish,
+// compact.  Partials and decisions go through b_part / b_dec.
+struct MatchPass {
+    const uint8_t* s8;
+    const int* sums;
+    const sgplan::Plan& plan;       // the counts of what tab points to
+    sgplan::TableView tab;          // device
+    float distmax, ratiomax;
+    int max_match;
+    int64_t out_rows;               // rows of d_out that may be written
+    int* d_counts;
+    long long* d_offs;
+    int* d_out;
+    const float* loc = nullptr;
+    int loc_stride = 2;
+    const sgk::GuidedParams* d_geom = nullptr;
+};
+int queue_match_pass(sgpu_ctx* ctx, const MatchPass& m);
+// The host has the pairs' counts: the pairs that fit cap form a prefix, whose matches come down
+// from d_out (want_matches false: counts only, cap is not looked at).  Returns the total, or
+// SGPU_ERANGE when it exceeds cap (counts are complete) or the return type.
+int download_fitting(sgpu_ctx* ctx, const int* counts, int npairs, const int* d_out, int* out_pairs,
+                     int64_t cap, bool want_matches = true);
 }  // namespace sgh

@@ -11,51 +11,11 @@ using namespace sgh;
 
 namespace {
 
-// where the sets come from: the last extract (images), or the caller's desc / scale, host memory
-// (uploaded here, after every check) or device memory (device)
-struct SelectInput {
-    bool images = false, device = false;
-    const uint8_t* desc = nullptr;
-    const float* scale = nullptr;
-    int stride = 1;   // floats between the scales of consecutive rows
-};
-
-size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
-
 // offsets that sgpu_match_batch would accept, before any size is taken from them
 int check_offsets(sgpu_ctx* ctx, const int64_t* off, int nsets) {
-    sgplan::Plan probe;
-    const int prc = sgplan::build_plan(off, nsets, nullptr, 0, false, 0, probe);
+    const int prc = probe_offsets(off, nsets);
     if (prc == sgplan::kPlanBadArgument) return ctx->fail(SGPU_EINVAL, "bad set offsets");
     if (prc != sgplan::kPlanOk) return ctx->fail(SGPU_ERANGE, "too many rows");
-    return SGPU_OK;
-}
-
-// the states sgpu_match_images refuses (feature_u8), before anything is queued
-int check_batch(sgpu_ctx* ctx) {
-    if (ctx->batch <= 0 || ctx->img_off.empty())
-        return ctx->fail(SGPU_EINVAL, "no extracted batch to select from");
-    if (!ctx->opt.descriptors) return ctx->fail(SGPU_EINVAL, "descriptors disabled (-sd)");
-    return SGPU_OK;
-}
-
-// host scales to the device: the floats that the rows of [0, total_rows) read
-int upload_scale(sgpu_ctx* ctx, const SelectInput& in, int64_t total_rows, const float** d_scale) {
-    const size_t floats = (size_t)(total_rows - 1) * in.stride + 1;
-    ALLOCCHK(ctx, ctx->p_scale.ensure(floats * sizeof(float)));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->p_scale.p, in.scale, floats * sizeof(float),
-                               hipMemcpyHostToDevice, ctx->stream));
-    *d_scale = ctx->p_scale.as<float>();
-    return SGPU_OK;
-}
-
-// the last extract's device keys [x, y, scale, orientation]: the scale is column 2 at stride 4
-int batch_scale(sgpu_ctx* ctx, const float** d_scale, int* stride) {
-    const float* keys = nullptr;
-    const int rc = sgpu_device_features(ctx, &keys, nullptr, nullptr);   // (gathers a multi-part batch)
-    if (rc != SGPU_OK) return rc;
-    *d_scale = keys ? keys + 2 : nullptr;
-    *stride = 4;
     return SGPU_OK;
 }
 
@@ -71,10 +31,10 @@ size_t offset_tables(unsigned char* tb, const int64_t* off, const std::vector<in
 }
 
 // The selection alone.  One table upload, one launch, one download, one synchronisation.
-int select_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, int top,
+int select_impl(sgpu_ctx* ctx, const SetSource& in, const int64_t* off, int nsets, int top,
                 int* out_index, int64_t* out_offsets) {
     if (top < 1) return ctx->fail(SGPU_EINVAL, "top < 1");
-    if (in.stride < 1) return ctx->fail(SGPU_EINVAL, "scale_stride < 1");
+    if (in.scale_stride < 1) return ctx->fail(SGPU_EINVAL, "scale_stride < 1");
     if (!out_index || !out_offsets) return ctx->fail(SGPU_EINVAL, "null outputs");
     if (const int rc = check_offsets(ctx, off, nsets)) return rc;
     const int64_t total_rows = nsets > 0 ? off[nsets] : 0;
@@ -84,12 +44,8 @@ int select_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, in
     const int64_t total_sub = sub[nsets];
     if (total_sub > 0) {
         hipStream_t st = ctx->stream;
-        const float* d_scale = in.scale;
-        if (in.images) {
-            if (const int rc = batch_scale(ctx, &d_scale, &in.stride)) return rc;
-        } else if (!in.device) {
-            if (const int rc = upload_scale(ctx, in, total_rows, &d_scale)) return rc;
-        }
+        DeviceSets sets;
+        if (const int rc = resolve_sets(ctx, in, total_rows, SET_SCALE, sets)) return rc;
         ctx->b_tables.resize(((size_t)nsets + 1) * 16);
         const size_t b_tab = offset_tables(ctx->b_tables.data(), off, sub, nsets);
         ALLOCCHK(ctx, ctx->b_plan.ensure(b_tab));
@@ -97,8 +53,8 @@ int select_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, in
         HIPCHK(ctx, hipMemcpyAsync(ctx->b_plan.p, ctx->b_tables.data(), b_tab, hipMemcpyHostToDevice, st));
         const auto* d_setoff = ctx->b_plan.as<long long>();
         const auto* d_suboff = reinterpret_cast<const int*>(d_setoff + nsets + 1);
-        HIPCHK(ctx, sgk::launch_select_top_scale(d_scale, in.stride, d_setoff, d_suboff, nsets, top,
-                                                 ctx->p_index.as<int>(), st));
+        HIPCHK(ctx, sgk::launch_select_top_scale(sets.scale, sets.scale_stride, d_setoff, d_suboff,
+                                                 nsets, top, ctx->p_index.as<int>(), st));
         HIPCHK(ctx, hipMemcpyAsync(out_index, ctx->p_index.p, (size_t)total_sub * sizeof(int),
                                    hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
@@ -111,11 +67,11 @@ int select_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, in
 // the gathered u8 rows, a caller's descriptors only] -> k_match_pairs, finish, count / scan / write
 // over the subsets -> [k_remap_matches, only when matches are wanted].  One table upload, the
 // counts' download and at most one of matches, two synchronisations, whatever nsets and npairs are.
-int prematch_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, const int* set_pairs,
+int prematch_impl(sgpu_ctx* ctx, const SetSource& in, const int64_t* off, int nsets, const int* set_pairs,
                   int npairs, int top, float distmax, float ratiomax, int mbm, int* out_counts,
                   int* out_pairs, int64_t cap) {
     if (top < 1) return ctx->fail(SGPU_EINVAL, "top < 1");
-    if (in.stride < 1) return ctx->fail(SGPU_EINVAL, "scale_stride < 1");
+    if (in.scale_stride < 1) return ctx->fail(SGPU_EINVAL, "scale_stride < 1");
     if (!out_counts) return ctx->fail(SGPU_EINVAL, "null out_counts");
     if (const int rc = check_offsets(ctx, off, nsets)) return rc;
     const int64_t total_rows = off[nsets];
@@ -151,46 +107,21 @@ int prematch_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, 
         return 0;
     }
 
-    // ---- everything is checked: the inputs
-    const uint8_t* rows = in.desc;   // what the gather reads: a caller's u8 rows, or the batch's s8 form
-    const int* row_sums = nullptr;
-    const float* d_scale = in.scale;
-    bool timing_started = false;
-    if (in.images) {
-        // a quantisation this call has to make counts into its device time, as in sgpu_match_images
-        timing_started = !ctx->f_ready;
-        if (timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-        if (const int rc = feature_u8(ctx)) return rc;
-        if (const int rc = batch_scale(ctx, &d_scale, &in.stride)) return rc;
-        rows = ctx->f_s8.as<uint8_t>();
-        row_sums = ctx->f_sums.as<int>();
-    } else if (!in.device) {
-        ALLOCCHK(ctx, ctx->b_desc.ensure((size_t)total_rows * 128));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->b_desc.p, in.desc, (size_t)total_rows * 128,
-                                   hipMemcpyHostToDevice, st));
-        rows = ctx->b_desc.as<uint8_t>();
-        if (const int rc = upload_scale(ctx, in, total_rows, &d_scale)) return rc;
-    }
+    // ---- everything is checked: the inputs.  The gather reads the batch's s8 form and sums, or a
+    // caller's u8 rows
+    DeviceSets sets;
+    if (const int rc = resolve_sets(ctx, in, total_rows, SET_DESC | SET_SCALE, sets)) return rc;
     if (const int rc = ensure_dist_table(ctx)) return rc;
 
     // ---- the tables in one buffer, one upload: the matcher's [items][sides][finish panels][pairs],
     // then [set offsets][subset offsets][the two subsets' offsets of every pair]
-    const size_t b_items = plan.items.size() * sizeof(sgplan::Item);
-    const size_t b_sides = plan.sides.size() * sizeof(sgplan::Side);
-    const size_t b_fp = plan.fpanels.size() * sizeof(sgplan::FinishPanel);
-    const size_t b_pairs = plan.pairs.size() * sizeof(sgplan::PairRec);
-    static_assert(sizeof(sgplan::Item) % 8 == 0 && sizeof(sgplan::Side) % 8 == 0 &&
-                  sizeof(sgplan::FinishPanel) % 8 == 0 && sizeof(sgplan::PairRec) % 8 == 0,
-                  "the set offsets stay 8-byte aligned");
-    const size_t o_off = b_items + b_sides + b_fp + b_pairs;
+    const sgplan::TableLayout lay = sgplan::table_layout(plan);
+    const size_t o_off = lay.bytes;
     const size_t b_off = ((size_t)nsets + 1) * sizeof(long long) + round8(((size_t)nsets + 1) * sizeof(int));
     const size_t o_psub = o_off + b_off;
     ctx->b_tables.resize(o_psub + (size_t)npairs * 2 * sizeof(int));
     unsigned char* tb = ctx->b_tables.data();
-    memcpy(tb, plan.items.data(), b_items);
-    memcpy(tb + b_items, plan.sides.data(), b_sides);
-    memcpy(tb + b_items + b_sides, plan.fpanels.data(), b_fp);
-    memcpy(tb + b_items + b_sides + b_fp, plan.pairs.data(), b_pairs);
+    sgplan::pack_tables(plan, tb);
     offset_tables(tb + o_off, off, sub, nsets);
     auto* h_psub = reinterpret_cast<int*>(tb + o_psub);
     for (int p = 0; p < npairs; p++) {
@@ -198,54 +129,40 @@ int prematch_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, 
         h_psub[2 * p + 1] = (int)sub[set_pairs[2 * p + 1]];
     }
     const int64_t out_rows = std::min<int64_t>(cap, plan.out_bound);
-    ALLOCCHK(ctx, ctx->b_plan.ensure(ctx->b_tables.size()));
-    ALLOCCHK(ctx, ctx->b_part.ensure((size_t)plan.part_total * sizeof(sgk::Top2)));
-    ALLOCCHK(ctx, ctx->b_dec.ensure((size_t)plan.dec_total * sizeof(int)));
-    // [offsets npairs + 1 (64-bit)][counts npairs]
-    ALLOCCHK(ctx, ctx->b_cnt.ensure((size_t)(npairs + 1) * sizeof(long long) + (size_t)npairs * sizeof(int)));
-    ALLOCCHK(ctx, ctx->b_out.ensure((size_t)std::max<int64_t>(out_rows, 1) * 2 * sizeof(int)));
+    // b_s8 / b_sums hold the gathered subsets' forms
+    if (const int rc = ensure_pair_buffers(ctx, plan, ctx->b_tables.size(), out_rows, npairs, total_sub))
+        return rc;
     ALLOCCHK(ctx, ctx->p_index.ensure((size_t)total_sub * sizeof(int)));
-    ALLOCCHK(ctx, ctx->b_s8.ensure((size_t)total_sub * 128));
-    ALLOCCHK(ctx, ctx->b_sums.ensure((size_t)total_sub * sizeof(int)));
     if (!in.images) ALLOCCHK(ctx, ctx->p_u8.ensure((size_t)total_sub * 128));
     HIPCHK(ctx, hipMemcpyAsync(ctx->b_plan.p, tb, ctx->b_tables.size(), hipMemcpyHostToDevice, st));
     const unsigned char* dt = ctx->b_plan.as<unsigned char>();
-    const auto* d_items = reinterpret_cast<const sgplan::Item*>(dt);
-    const auto* d_sides = reinterpret_cast<const sgplan::Side*>(dt + b_items);
-    const auto* d_fp = reinterpret_cast<const sgplan::FinishPanel*>(dt + b_items + b_sides);
-    const auto* d_pairs = reinterpret_cast<const sgplan::PairRec*>(dt + b_items + b_sides + b_fp);
     const auto* d_setoff = reinterpret_cast<const long long*>(dt + o_off);
     const auto* d_suboff = reinterpret_cast<const int*>(d_setoff + nsets + 1);
     const auto* d_psub = reinterpret_cast<const int*>(dt + o_psub);
     long long* d_offs = ctx->b_cnt.as<long long>();
     int* d_counts = reinterpret_cast<int*>(d_offs + npairs + 1);
     int* d_index = ctx->p_index.as<int>();
-    uint8_t* d_s8 = ctx->b_s8.as<uint8_t>();
-    int* d_sums = ctx->b_sums.as<int>();
 
     // ---- the queue
-    if (!timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-    HIPCHK(ctx, sgk::launch_select_top_scale(d_scale, in.stride, d_setoff, d_suboff, nsets, top,
-                                             d_index, st));
+    if (!sets.timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    HIPCHK(ctx, sgk::launch_select_top_scale(sets.scale, sets.scale_stride, d_setoff, d_suboff, nsets,
+                                             top, d_index, st));
+    DeviceSets subs;   // the gathered subsets
     if (in.images) {
         // the matcher's forms exist: gather them, no prep
-        HIPCHK(ctx, sgk::launch_gather_rows(rows, row_sums, d_setoff, d_suboff, d_index, nsets, d_s8,
-                                            d_sums, st));
+        HIPCHK(ctx, sgk::launch_gather_rows(sets.s8, sets.sums, d_setoff, d_suboff, d_index, nsets,
+                                            ctx->b_s8.as<uint8_t>(), ctx->b_sums.as<int>(), st));
+        subs.s8 = ctx->b_s8.as<uint8_t>();
+        subs.sums = ctx->b_sums.as<int>();
     } else {
-        HIPCHK(ctx, sgk::launch_gather_rows(rows, nullptr, d_setoff, d_suboff, d_index, nsets,
+        HIPCHK(ctx, sgk::launch_gather_rows(sets.u8, nullptr, d_setoff, d_suboff, d_index, nsets,
                                             ctx->p_u8.as<uint8_t>(), nullptr, st));
-        sgk::PrepSet prep{ctx->p_u8.as<uint8_t>(), (int)total_sub, d_s8};
-        prep.sums = d_sums;
-        HIPCHK(ctx, sgk::launch_prep_set(prep, st));
+        subs.u8 = ctx->p_u8.as<uint8_t>();
+        if (const int rc = derive_s8(ctx, subs, total_sub)) return rc;
     }
-    HIPCHK(ctx, sgk::launch_match_pairs(d_s8, d_items, (int)plan.items.size(),
-                                        ctx->b_part.as<sgk::Top2>(), st));
-    HIPCHK(ctx, sgk::launch_match_pairs_finish(ctx->b_part.as<sgk::Top2>(), d_sides, d_fp,
-                                               (int)plan.fpanels.size(), d_sums,
-                                               ctx->m_dist.as<float>(), distmax, ratiomax,
-                                               ctx->b_dec.as<int>(), st));
-    HIPCHK(ctx, sgk::launch_match_pairs_compact(ctx->b_dec.as<int>(), d_pairs, npairs, top, out_rows,
-                                                d_counts, d_offs, ctx->b_out.as<int>(), st));
+    const MatchPass pass{subs.s8, subs.sums, plan, sgplan::view_tables(lay, dt), distmax, ratiomax,
+                         top, out_rows, d_counts, d_offs, ctx->b_out.as<int>()};
+    if (const int rc = queue_match_pass(ctx, pass)) return rc;
     if (want_matches && out_rows > 0)
         HIPCHK(ctx, sgk::launch_remap_matches(d_counts, d_offs, d_psub, d_index, npairs, out_rows,
                                               ctx->b_out.as<int>(), st));
@@ -254,23 +171,7 @@ int prematch_impl(sgpu_ctx* ctx, SelectInput in, const int64_t* off, int nsets, 
                                hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     (void)hipEventElapsedTime(&ctx->timing[T_PREMATCH], ctx->ev[1], ctx->ev[2]);
-    int64_t total = 0, fit = 0;
-    bool fits = true;
-    for (int p = 0; p < npairs; p++) {
-        total += out_counts[p];
-        fits = fits && total <= cap;
-        if (fits) fit = total;
-    }
-    if (total > INT_MAX) return ctx->fail(SGPU_ERANGE, "match total exceeds the return type");
-    if (!want_matches) return (int)total;
-    // the pairs that fit form a prefix (the offsets only grow): copy their matches
-    if (fit > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(out_pairs, ctx->b_out.p, (size_t)fit * 2 * sizeof(int),
-                                   hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    if (total > cap) return ctx->fail(SGPU_ERANGE, "matches exceed cap (counts are complete)");
-    return (int)total;
+    return download_fitting(ctx, out_counts, npairs, ctx->b_out.as<int>(), out_pairs, cap, want_matches);
 }
 
 }  // namespace
@@ -283,18 +184,18 @@ int sgpu_select_top_scale_batch(sgpu_ctx* ctx, const float* scale, int scale_str
     if (!ctx) return SGPU_EINVAL;
     if (nsets < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad select arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    SelectInput in;
+    SetSource in;
     in.device = (flags & SGPU_INPUT_DEVICE) != 0;
     in.scale = scale;
-    in.stride = scale_stride;
+    in.scale_stride = scale_stride;
     return select_impl(ctx, in, set_offsets, nsets, top, out_index, out_offsets);
 }
 
 int sgpu_select_top_scale_images(sgpu_ctx* ctx, int top, int* out_index, int64_t* out_offsets) {
     if (!ctx) return SGPU_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (const int rc = check_batch(ctx)) return rc;
-    SelectInput in;
+    if (const int rc = check_batch(ctx, "select from")) return rc;
+    SetSource in;
     in.images = true;
     return select_impl(ctx, in, ctx->img_off.data(), ctx->batch, top, out_index, out_offsets);
 }
@@ -306,11 +207,11 @@ int sgpu_prematch_batch(sgpu_ctx* ctx, const uint8_t* desc, const float* scale, 
     if (!ctx) return SGPU_EINVAL;
     if (nsets < 0 || npairs < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad prematch arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    SelectInput in;
+    SetSource in;
     in.device = (flags & SGPU_INPUT_DEVICE) != 0;
     in.desc = desc;
     in.scale = scale;
-    in.stride = scale_stride;
+    in.scale_stride = scale_stride;
     return prematch_impl(ctx, in, set_offsets, nsets, set_pairs, npairs, top, distmax, ratiomax,
                          mutual_best_match, out_counts, out_pairs, cap);
 }
@@ -321,8 +222,8 @@ int sgpu_prematch_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, int 
     if (!ctx) return SGPU_EINVAL;
     if (npairs < 0) return ctx->fail(SGPU_EINVAL, "bad prematch arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (const int rc = check_batch(ctx)) return rc;
-    SelectInput in;
+    if (const int rc = check_batch(ctx, "select from")) return rc;
+    SetSource in;
     in.images = true;
     return prematch_impl(ctx, in, ctx->img_off.data(), ctx->batch, image_pairs, npairs, top, distmax,
                          ratiomax, mutual_best_match, out_counts, out_pairs, cap);

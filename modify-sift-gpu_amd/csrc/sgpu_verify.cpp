@@ -12,13 +12,6 @@ using namespace sgh;
 
 namespace {
 
-// where the sets come from: the last extract (images), or the caller's desc / loc, host memory
-// (uploaded here, after every check) or device memory (device)
-struct VerifyInput {
-    bool images = false, device = false;
-    const uint8_t* desc = nullptr;
-    const float* loc = nullptr;
-};
 struct VerifyOutput {
     float* H;
     int* inliers_H;
@@ -30,15 +23,13 @@ struct VerifyOutput {
     int* counts;
 };
 
-size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
-
 // The whole call.  Queue order on ctx->stream: [prep] k_match_pairs, finish, compact (cap = the
 // plan's bound) -> k_verify_pair_recs -> k_verify_gather -> per model: k_estimate_pairs (guarded),
 // k_estimate_finish, k_estimate_refine -> k_verify_guided_params -> k_match_pairs_guided, finish,
 // compact (the caller's cap, its own counts / offsets).  Two memsets (all slots, all error
 // flags), one table upload, one result download, two synchronisations, whatever npairs and
 // refine_rounds are.
-int verify_impl(sgpu_ctx* ctx, const VerifyInput& in, const int64_t* off, int nsets,
+int verify_impl(sgpu_ctx* ctx, const SetSource& in, const int64_t* off, int nsets,
                 const int* set_pairs, int npairs, const sgpu_verify_params* vp,
                 const VerifyOutput& out) {
     if (!vp) return ctx->fail(SGPU_EINVAL, "null verify params");
@@ -86,56 +77,18 @@ int verify_impl(sgpu_ctx* ctx, const VerifyInput& in, const int64_t* off, int ns
     if (!in.images && !in.loc) return ctx->fail(SGPU_EINVAL, "verify needs locations");
 
     // ---- everything is checked: the inputs
-    const uint8_t* u8 = in.desc;
-    const uint8_t* s8 = nullptr;
-    const int* sums = nullptr;
-    const float* loc = in.loc;
-    int stride = 2;
-    bool timing_started = false;
-    if (in.images) {
-        // a quantisation this call has to make counts into its device time, as in
-        // sgpu_match_images
-        timing_started = !ctx->f_ready;
-        if (timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-        int rc = feature_u8(ctx);
-        if (rc != SGPU_OK) return rc;
-        rc = sgpu_device_features(ctx, &loc, nullptr, nullptr);
-        if (rc != SGPU_OK) return rc;
-        u8 = ctx->f_u8.as<uint8_t>();
-        s8 = ctx->f_s8.as<uint8_t>();
-        sums = ctx->f_sums.as<int>();
-        stride = 4;
-    } else if (!in.device) {
-        ALLOCCHK(ctx, ctx->b_desc.ensure((size_t)total_rows * 128));
-        ALLOCCHK(ctx, ctx->b_loc.ensure((size_t)total_rows * 2 * sizeof(float)));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->b_desc.p, in.desc, (size_t)total_rows * 128,
-                                   hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->b_loc.p, in.loc, (size_t)total_rows * 2 * sizeof(float),
-                                   hipMemcpyHostToDevice, st));
-        u8 = ctx->b_desc.as<uint8_t>();
-        loc = ctx->b_loc.as<float>();
-    }
+    DeviceSets sets;
+    if (const int rc = resolve_sets(ctx, in, total_rows, SET_DESC | SET_LOC, sets)) return rc;
     if (const int rc = ensure_dist_table(ctx)) return rc;
 
     // ---- the tables in one buffer, one upload: the matcher's [items][sides][finish panels]
     // [pairs], then the estimator's [pairs][items]; the estimator's pairs carry their sets' first
     // rows, k_verify_pair_recs fills moff / m on the device
-    const size_t b_items = plan.items.size() * sizeof(sgplan::Item);
-    const size_t b_sides = plan.sides.size() * sizeof(sgplan::Side);
-    const size_t b_fp = plan.fpanels.size() * sizeof(sgplan::FinishPanel);
-    const size_t b_pairs = plan.pairs.size() * sizeof(sgplan::PairRec);
-    const size_t b_epairs = n * sizeof(sgeo::PairRec);
-    const size_t b_eitems = (size_t)nitems * sizeof(sgeo::Item);
-    static_assert(sizeof(sgplan::Item) % 8 == 0 && sizeof(sgplan::Side) % 8 == 0 &&
-                  sizeof(sgplan::FinishPanel) % 8 == 0 && sizeof(sgplan::PairRec) % 8 == 0,
-                  "the estimator's pairs stay 8-byte aligned");
-    const size_t o_epairs = b_items + b_sides + b_fp + b_pairs, o_eitems = o_epairs + b_epairs;
-    ctx->b_tables.resize(o_eitems + b_eitems);
+    const sgplan::TableLayout lay = sgplan::table_layout(plan);
+    const size_t o_epairs = lay.bytes, o_eitems = o_epairs + n * sizeof(sgeo::PairRec);
+    ctx->b_tables.resize(o_eitems + (size_t)nitems * sizeof(sgeo::Item));
     unsigned char* tb = ctx->b_tables.data();
-    memcpy(tb, plan.items.data(), b_items);
-    memcpy(tb + b_items, plan.sides.data(), b_sides);
-    memcpy(tb + b_items + b_sides, plan.fpanels.data(), b_fp);
-    memcpy(tb + b_items + b_sides + b_fp, plan.pairs.data(), b_pairs);
+    sgplan::pack_tables(plan, tb);
     auto* h_epairs = reinterpret_cast<sgeo::PairRec*>(tb + o_epairs);
     auto* h_eitems = reinterpret_cast<sgeo::Item*>(tb + o_eitems);
     for (int p = 0; p < npairs; p++) {
@@ -160,23 +113,15 @@ int verify_impl(sgpu_ctx* ctx, const VerifyInput& in, const int64_t* off, int ns
     const size_t b_vbuf = o_geom + n * sizeof(sgk::GuidedParams);
     const int64_t bound = plan.out_bound;   // the putative pass has no user cap
     const int64_t out_rows = std::min<int64_t>(cap, bound);
-    ALLOCCHK(ctx, ctx->b_plan.ensure(ctx->b_tables.size()));
-    ALLOCCHK(ctx, ctx->b_part.ensure((size_t)plan.part_total * sizeof(sgk::Top2)));
-    ALLOCCHK(ctx, ctx->b_dec.ensure((size_t)plan.dec_total * sizeof(int)));
-    ALLOCCHK(ctx, ctx->b_out.ensure((size_t)std::max<int64_t>(bound, 1) * 2 * sizeof(int)));
+    // b_out by the plan's bound, not the cap; the counts and offsets of both passes are v_buf's
+    if (const int rc = ensure_pair_buffers(ctx, plan, ctx->b_tables.size(), bound, 0,
+                                           sets.s8 && sets.sums ? 0 : total_rows))
+        return rc;
     ALLOCCHK(ctx, ctx->e_pts.ensure((size_t)std::max<int64_t>(bound, 1) * sizeof(float4)));
     ALLOCCHK(ctx, ctx->v_buf.ensure(b_vbuf));
-    if (!s8 || !sums) {
-        ALLOCCHK(ctx, ctx->b_s8.ensure((size_t)total_rows * 128));
-        ALLOCCHK(ctx, ctx->b_sums.ensure((size_t)total_rows * sizeof(int)));
-    }
     ctx->v_result.resize(b_result);
     HIPCHK(ctx, hipMemcpyAsync(ctx->b_plan.p, tb, ctx->b_tables.size(), hipMemcpyHostToDevice, st));
     unsigned char* dt = ctx->b_plan.as<unsigned char>();
-    const auto* d_items = reinterpret_cast<const sgplan::Item*>(dt);
-    const auto* d_sides = reinterpret_cast<const sgplan::Side*>(dt + b_items);
-    const auto* d_fp = reinterpret_cast<const sgplan::FinishPanel*>(dt + b_items + b_sides);
-    const auto* d_pairs = reinterpret_cast<const sgplan::PairRec*>(dt + b_items + b_sides + b_fp);
     auto* d_epairs = reinterpret_cast<sgeo::PairRec*>(dt + o_epairs);
     const auto* d_eitems = reinterpret_cast<const sgeo::Item*>(dt + o_eitems);
     unsigned char* dv = ctx->v_buf.as<unsigned char>();
@@ -190,33 +135,22 @@ int verify_impl(sgpu_ctx* ctx, const VerifyInput& in, const int64_t* off, int ns
     int* d_err = reinterpret_cast<int*>(dv + o_result + r_err);
     int* d_rounds = reinterpret_cast<int*>(dv + o_rounds);
     auto* d_geom = reinterpret_cast<sgk::GuidedParams*>(dv + o_geom);
-    sgk::Top2* d_part = ctx->b_part.as<sgk::Top2>();
-    int* d_dec = ctx->b_dec.as<int>();
     int* d_out = ctx->b_out.as<int>();
     float4* d_pts = ctx->e_pts.as<float4>();
 
     // ---- the queue
-    if (!timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-    if (!s8 || !sums) {
-        sgk::PrepSet prep{u8, (int)total_rows, ctx->b_s8.as<uint8_t>()};
-        prep.sums = ctx->b_sums.as<int>();
-        HIPCHK(ctx, sgk::launch_prep_set(prep, st));
-        s8 = ctx->b_s8.as<uint8_t>();
-        sums = ctx->b_sums.as<int>();
-    }
+    if (!sets.timing_started) HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    if (const int rc = derive_s8(ctx, sets, total_rows)) return rc;
     HIPCHK(ctx, hipMemsetAsync(d_slots, 0, b_slots, st));
     HIPCHK(ctx, hipMemsetAsync(d_err, 0, (size_t)nm * sizeof(int), st));
     // pass 1: the putative matches, all of them, in b_out
-    HIPCHK(ctx, sgk::launch_match_pairs(s8, d_items, (int)plan.items.size(), d_part, st));
-    HIPCHK(ctx, sgk::launch_match_pairs_finish(d_part, d_sides, d_fp, (int)plan.fpanels.size(), sums,
-                                               ctx->m_dist.as<float>(), vp->distmax, vp->ratiomax,
-                                               d_dec, st));
-    HIPCHK(ctx, sgk::launch_match_pairs_compact(d_dec, d_pairs, npairs, vp->max_match, bound,
-                                                d_counts1, d_offs1, d_out, st));
+    MatchPass pass{sets.s8, sets.sums, plan, sgplan::view_tables(lay, dt), vp->distmax, vp->ratiomax,
+                   vp->max_match, bound, d_counts1, d_offs1, d_out};
+    if (const int rc = queue_match_pass(ctx, pass)) return rc;
     // the estimator's view of them
     HIPCHK(ctx, sgk::launch_verify_pair_recs(d_offs1, d_counts1, npairs, d_epairs, st));
-    HIPCHK(ctx, sgk::launch_verify_gather(loc, stride, d_epairs, npairs, d_out, d_offs1 + npairs,
-                                          bound, d_pts, st));
+    HIPCHK(ctx, sgk::launch_verify_gather(sets.loc, sets.loc_stride, d_epairs, npairs, d_out,
+                                          d_offs1 + npairs, bound, d_pts, st));
     const float* d_H = nullptr;
     const float* d_F = nullptr;
     for (int k = 0; k < nm; k++) {
@@ -238,13 +172,13 @@ int verify_impl(sgpu_ctx* ctx, const VerifyInput& in, const int64_t* off, int ns
     // pass 2 under the device's matrices: b_part / b_dec again, and b_out, which the gather has
     // consumed; its own counts and offsets, so that the putative counts survive
     HIPCHK(ctx, sgk::launch_verify_guided_params(d_H, d_F, vp->hdistmax, vp->fdistmax, npairs, d_geom, st));
-    HIPCHK(ctx, sgk::launch_match_pairs_guided(s8, d_items, (int)plan.items.size(), d_part, loc,
-                                               stride, d_geom, st));
-    HIPCHK(ctx, sgk::launch_match_pairs_finish(d_part, d_sides, d_fp, (int)plan.fpanels.size(), sums,
-                                               ctx->m_dist.as<float>(), vp->distmax, vp->ratiomax,
-                                               d_dec, st));
-    HIPCHK(ctx, sgk::launch_match_pairs_compact(d_dec, d_pairs, npairs, vp->max_match, out_rows,
-                                                d_counts2, d_offs2, d_out, st));
+    pass.out_rows = out_rows;
+    pass.d_counts = d_counts2;
+    pass.d_offs = d_offs2;
+    pass.loc = sets.loc;
+    pass.loc_stride = sets.loc_stride;
+    pass.d_geom = d_geom;
+    if (const int rc = queue_match_pass(ctx, pass)) return rc;
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], st));
     // ---- nothing has come down or been waited for so far: the one result block
     unsigned char* hr = ctx->v_result.data();
@@ -266,22 +200,7 @@ int verify_impl(sgpu_ctx* ctx, const VerifyInput& in, const int64_t* off, int ns
         err |= e;
     }
     if (err) return ctx->fail(SGPU_ENODEV, "estimate: a regenerated winner's inlier count differs from its score");
-    // the pairs that fit form a prefix (the offsets only grow): copy their matches
-    int64_t total = 0, fit = 0;
-    bool fits = true;
-    for (int p = 0; p < npairs; p++) {
-        total += out.counts[p];
-        fits = fits && total <= cap;
-        if (fits) fit = total;
-    }
-    if (fit > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(out.pairs, d_out, (size_t)fit * 2 * sizeof(int),
-                                   hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    if (total > cap) return ctx->fail(SGPU_ERANGE, "matches exceed cap (counts are complete)");
-    if (total > INT_MAX) return ctx->fail(SGPU_ERANGE, "match total exceeds the return type");
-    return (int)total;
+    return download_fitting(ctx, out.counts, npairs, d_out, out.pairs, cap);
 }
 
 }  // namespace
@@ -311,7 +230,7 @@ int sgpu_verify_batch(sgpu_ctx* ctx, const uint8_t* desc, const float* loc,
     if (!ctx) return SGPU_EINVAL;
     if (nsets < 0 || npairs < 0 || !set_offsets) return ctx->fail(SGPU_EINVAL, "bad verify batch arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    VerifyInput in;
+    SetSource in;
     in.device = (flags & SGPU_INPUT_DEVICE) != 0;
     in.desc = desc;
     in.loc = loc;
@@ -328,10 +247,8 @@ int sgpu_verify_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
     if (npairs < 0) return ctx->fail(SGPU_EINVAL, "bad verify arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // the states sgpu_match_images_guided refuses (feature_u8), before anything is queued
-    if (ctx->batch <= 0 || ctx->img_off.empty())
-        return ctx->fail(SGPU_EINVAL, "no extracted batch to verify on");
-    if (!ctx->opt.descriptors) return ctx->fail(SGPU_EINVAL, "descriptors disabled (-sd)");
-    VerifyInput in;
+    if (const int rc = check_batch(ctx, "verify on")) return rc;
+    SetSource in;
     in.images = true;
     return verify_impl(ctx, in, ctx->img_off.data(), ctx->batch, image_pairs, npairs, params,
                        VerifyOutput{out_H, out_inliers_H, out_F, out_inliers_F, out_putative,

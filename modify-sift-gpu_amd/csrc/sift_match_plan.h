@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace sgplan {
@@ -133,6 +134,54 @@ inline int build_plan(const int64_t* off, int nsets, const int* set_pairs, int n
         }
     }
     return kPlanOk;
+}
+
+// The four tables as the kernels read them, in one block: [items][sides][finish panels][pairs].
+// The layout is the same in the host block that is packed and in its device copy; a caller's own
+// trailer starts at `bytes`.
+struct TableLayout {
+    size_t items = 0, sides = 0, fpanels = 0, pairs = 0;   // byte offsets
+    size_t bytes = 0;
+};
+struct TableView {
+    const Item* items;
+    const Side* sides;
+    const FinishPanel* fpanels;
+    const PairRec* pairs;
+};
+static_assert(sizeof(sgplan::Item) % 8 == 0 && sizeof(sgplan::Side) % 8 == 0 &&
+              sizeof(sgplan::FinishPanel) % 8 == 0 && sizeof(sgplan::PairRec) % 8 == 0,
+              "every table, and the trailer after them, stays 8-byte aligned");
+
+template <class T> size_t table_bytes(const std::vector<T>& v) { return v.size() * sizeof(T); }
+
+inline TableLayout table_layout(const Plan& plan) {
+    TableLayout l;
+    l.sides = l.items + table_bytes(plan.items);
+    l.fpanels = l.sides + table_bytes(plan.sides);
+    l.pairs = l.fpanels + table_bytes(plan.fpanels);
+    l.bytes = l.pairs + table_bytes(plan.pairs);
+    return l;
+}
+
+// dst: table_layout(plan).bytes bytes (not read or written when that is 0)
+inline void pack_tables(const Plan& plan, unsigned char* dst) {
+    const TableLayout l = table_layout(plan);
+    auto put = [dst](size_t at, const auto& v) {
+        if (!v.empty()) std::memcpy(dst + at, v.data(), table_bytes(v));
+    };
+    put(l.items, plan.items);
+    put(l.sides, plan.sides);
+    put(l.fpanels, plan.fpanels);
+    put(l.pairs, plan.pairs);
+}
+
+// the tables of a block at base, host or device memory (nothing is dereferenced here)
+inline TableView view_tables(const TableLayout& l, const unsigned char* base) {
+    return TableView{reinterpret_cast<const Item*>(base + l.items),
+                     reinterpret_cast<const Side*>(base + l.sides),
+                     reinterpret_cast<const FinishPanel*>(base + l.fpanels),
+                     reinterpret_cast<const PairRec*>(base + l.pairs)};
 }
 
 }  // namespace sgplan

@@ -566,25 +566,38 @@ class SiftContext:
                     "sgpu_copy_features_u8")
         return out
 
+    @staticmethod
+    def _default_cap(first, sizes, limit):
+        """The capacity that holds every pair's matches: min(rows of its first set, limit) summed
+        over the pairs; 0 where an index lies outside the sets (the library refuses that list)."""
+        first = np.asarray(first, np.int64).reshape(-1)
+        ok = len(first) and limit > 0 and (first >= 0).all() and (first < len(sizes)).all()
+        return int(np.minimum(np.asarray(sizes, np.int64)[first], limit).sum()) if ok else 0
+
+    def _fitting(self, rc, what, out, counts, cap, verified=None):
+        """One [m, 2] array per pair of the matches a call brought down: the pairs that fit cap form
+        a prefix.  SGPU_ERANGE raises MatchOverflow with them (and .verified, where given)."""
+        if rc < 0 and rc != SGPU_ERANGE:
+            self._check(rc, what)
+        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        res = [out[offs[p]:offs[p + 1]].copy() for p in range(len(counts)) if offs[p + 1] <= cap]
+        if rc == SGPU_ERANGE:
+            e = MatchOverflow(counts.copy(), res)
+            if verified is not None:
+                e.verified = verified
+            raise e
+        return res
+
     def _pair_results(self, call, pairs, sizes, max_match, cap):
         pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         npairs = len(pr)
         if max_match is None:
             max_match = int(max(sizes)) if len(sizes) else 0
-        if cap is None:
-            ok = (pr >= 0).all() and (pr < len(sizes)).all()
-            cap = int(sum(min(int(sizes[a]), max_match) for a in pr[:, 0])) if ok and max_match > 0 else 0
-        out = np.zeros((max(int(cap), 1), 2), np.int32)
+        cap = self._default_cap(pr[:, 0], sizes, max_match) if cap is None else int(cap)
+        out = np.zeros((max(cap, 1), 2), np.int32)
         counts = np.zeros(max(npairs, 1), np.int32)
-        rc = call(pr, npairs, int(max_match), out, int(cap), counts)
-        counts = counts[:npairs]
-        if rc < 0 and rc != SGPU_ERANGE:
-            self._check(rc, "match batch")
-        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
-        res = [out[offs[p]:offs[p + 1]].copy() for p in range(npairs) if offs[p + 1] <= cap]
-        if rc == SGPU_ERANGE:
-            raise MatchOverflow(counts.copy(), res)
-        return res
+        rc = call(pr, npairs, int(max_match), out, cap, counts)
+        return self._fitting(rc, "match batch", out, counts[:npairs], cap)
 
     def match_batch(self, desc_u8: np.ndarray, offsets, pairs, distmax=0.7, ratiomax=0.8, mbm=1,
                     max_match=None, cap=None):
@@ -790,10 +803,7 @@ class SiftContext:
         vp = self.verify_params(**params)
         pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         npairs = len(pr)
-        if cap is None:
-            ok = (pr >= 0).all() and (pr < len(sizes)).all()
-            cap = int(sum(min(int(sizes[a]), vp.max_match) for a in pr[:, 0])) if ok and vp.max_match > 0 else 0
-        cap = int(cap)
+        cap = self._default_cap(pr[:, 0], sizes, vp.max_match) if cap is None else int(cap)
         out = np.zeros((max(cap, 1), 2), np.int32)
         counts = np.zeros(max(npairs, 1), np.int32)
         putative = np.zeros(max(npairs, 1), np.int32)
@@ -803,19 +813,10 @@ class SiftContext:
         rc = call(pr.ctypes.data if npairs else None, npairs, ctypes.byref(vp), ptr(models[0]),
                   ptr(inliers[0]), ptr(models[1]), ptr(inliers[1]), putative.ctypes.data,
                   out.ctypes.data, cap, counts.ctypes.data)
-        if rc < 0 and rc != SGPU_ERANGE:
-            self._check(rc, "verify")
-        counts = counts[:npairs]
-        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
-        res = [out[offs[p]:offs[p + 1]].copy() for p in range(npairs) if offs[p + 1] <= cap]
         ms = [None if m is None else m[:npairs].reshape(npairs, 3, 3).copy() for m in models]
         ins = [None if i is None else i[:npairs].copy() for i in inliers]
         rest = (ms[0], ins[0], ms[1], ins[1], putative[:npairs].copy())
-        if rc == SGPU_ERANGE:
-            e = MatchOverflow(counts.copy(), res)
-            e.verified = rest
-            raise e
-        return (res,) + rest
+        return (self._fitting(rc, "verify", out, counts[:npairs], cap, rest),) + rest
 
     def verify_batch(self, desc_u8, loc, offsets, pairs, H=True, F=False, cap=None,
                      device_ptrs=None, **params):
@@ -938,23 +939,16 @@ class SiftContext:
         counts = np.zeros(max(npairs, 1), np.int32)
         out = None
         if matches:
-            if cap is None:
-                ok = npairs == 0 or ((first >= 0).all() and (first < nsets).all())
-                cap = int(np.minimum(np.asarray(sizes)[first], top).sum()) if ok and npairs and top > 0 else 0
-            cap = int(cap)
+            cap = self._default_cap(first, sizes, top) if cap is None else int(cap)
             out = np.zeros((max(cap, 1), 2), np.int32)
         rc = call(ptr, npairs, counts.ctypes.data, None if out is None else out.ctypes.data,
                   cap if matches else 0)
         counts = counts[:npairs]
-        if rc < 0 and rc != SGPU_ERANGE:
-            self._check(rc, "prematch")
         if not matches:
+            if rc < 0 and rc != SGPU_ERANGE:
+                self._check(rc, "prematch")
             return counts.copy(), None
-        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
-        res = [out[offs[p]:offs[p + 1]].copy() for p in range(npairs) if offs[p + 1] <= cap]
-        if rc == SGPU_ERANGE:
-            raise MatchOverflow(counts.copy(), res)
-        return counts.copy(), res
+        return counts.copy(), self._fitting(rc, "prematch", out, counts, cap)
 
     def prematch_batch(self, desc_u8, scale, offsets, pairs=None, top=100, distmax=0.7, ratiomax=0.8,
                        mbm=1, matches=True, cap=None, stride=1, device_ptrs=None):

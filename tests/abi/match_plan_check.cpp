@@ -3,6 +3,7 @@
 // property holds; a failure prints the property and exits 1.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <set>
 #include <tuple>
@@ -142,7 +143,51 @@ static void build_for(const std::vector<int>& sizes, const std::vector<std::pair
                        max_match, plan) == kPlanOk);
 }
 
+// The table block (table_layout, pack_tables, view_tables): the size is the sum of the four tables
+// and a multiple of 8, packing and viewing round-trip every table byte for byte, and a trailer
+// written at `bytes` leaves the last table alone.  The block is allocated at its exact size, so
+// that ASan sees a write past it.
+template <class T>
+static void same_bytes(const T* seen, const std::vector<T>& want) {
+    REQUIRE(want.empty() || std::memcmp(seen, want.data(), want.size() * sizeof(T)) == 0);
+}
+static void check_tables(const char* name, const std::vector<int>& sizes,
+                         const std::vector<std::pair<int, int>>& pairs, bool mutual) {
+    Plan plan;
+    build_for(sizes, pairs, mutual, 1 << 30, plan);
+    g_case = name;
+    const TableLayout l = table_layout(plan);
+    REQUIRE(l.bytes == plan.items.size() * sizeof(Item) + plan.sides.size() * sizeof(Side) +
+                           plan.fpanels.size() * sizeof(FinishPanel) +
+                           plan.pairs.size() * sizeof(PairRec));
+    REQUIRE(l.bytes % 8 == 0);
+    REQUIRE(l.items == 0 && l.items <= l.sides && l.sides <= l.fpanels && l.fpanels <= l.pairs &&
+            l.pairs <= l.bytes);
+    const size_t trailer = 24;
+    std::vector<unsigned char> block(l.bytes + trailer, 0xA5);
+    pack_tables(plan, block.data());
+    for (size_t k = 0; k < trailer; k++) REQUIRE(block[l.bytes + k] == 0xA5);   // packing stops at bytes
+    std::memset(block.data() + l.bytes, 0x5A, trailer);
+    const TableView v = view_tables(l, block.data());
+    same_bytes(v.items, plan.items);
+    same_bytes(v.sides, plan.sides);
+    same_bytes(v.fpanels, plan.fpanels);
+    same_bytes(v.pairs, plan.pairs);
+    REQUIRE(reinterpret_cast<const unsigned char*>(v.pairs + plan.pairs.size()) == block.data() + l.bytes);
+}
+
 int main() {
+    for (int mutual = 0; mutual < 2; mutual++) {
+        check_tables("tables 1x1", {1, 1}, {{0, 1}}, mutual != 0);
+        check_tables("tables 129x257", {129, 257}, {{0, 1}}, mutual != 0);
+        check_tables("tables with an empty set", {0, 5, 130}, {{0, 1}, {1, 2}, {2, 0}}, mutual != 0);
+    }
+    {
+        g_case = "empty tables";
+        const Plan none;   // no pair at all: nothing to pack, dst is not touched
+        REQUIRE(table_layout(none).bytes == 0);
+        pack_tables(none, nullptr);
+    }
     // the sets and pair list of the GPU size test
     const std::vector<int> sizes = {0, 1, 127, 128, 129, 257, 700, 3000};
     std::vector<std::pair<int, int>> pairs;
