@@ -516,6 +516,21 @@ int sgpu_debug_set_schedule(sgpu_ctx* ctx, int trio, int pairs);
 #define SGPU_DUO_STRIPS_WAVE 1
 #define SGPU_DUO_STRIPS_COOP 2
 int sgpu_debug_set_duo_strips(sgpu_ctx* ctx, int mode);
+/* The last Gaussian level of every octave, a test / A-B hook -- the same features
+ * in every mode.  Only the last DoG plane reads that level, and ComputeKEY reads that plane only
+ * around a candidate of the top DoG level.  LAZY: the pyramid leaves the level out; the
+ * wave-streaming extremum kernel marks the top DoG level's undecided pixels in the keypoint mask,
+ * and k_extrema_top evaluates the level at their 3 x 3 neighbourhoods (the dense filter's bits),
+ * stores those values and decides them; the rest of the level's plane holds stale data.  DENSE:
+ * every level filtered for every pixel.  RULE (shipped): lazy where the batch is too large for the
+ * tile extremum kernel, dense otherwise.  Whatever the mode, a batch whose extremum pass is the tile
+ * kernel is dense.  SGPU_TOP_LEVEL=dense / lazy at context creation sets the same.
+ * sgpu_last_pyramid_launches reports the filters that ran; sgpu_debug_gaussian returns the dense
+ * level in every mode (it filters a lazy octave's last level on first request). */
+#define SGPU_TOP_LEVEL_RULE 0
+#define SGPU_TOP_LEVEL_DENSE 1
+#define SGPU_TOP_LEVEL_LAZY 2
+int sgpu_debug_set_top_level(sgpu_ctx* ctx, int mode);
 /* Plain mutual matching (ratiomax <= 1) decides the listed columns over the rows of set 1 that can
  * change a decision -- those with some dot at or above the smallest second value that fails the
  * ratio test against the weakest passing row maximum -- instead of all of set 1 (on != 0, the
@@ -553,6 +568,11 @@ int sgpu_debug_gaussian(sgpu_ctx* ctx, int image, int octave, int level, float* 
 /* Detected (pre-orientation) keypoints of the batch in reference order: per entry
  * {col, row, level_id, image} ints and {dx, dy, ds, pad} floats.  Returns count via *n. */
 int sgpu_debug_candidates(sgpu_ctx* ctx, int* ints, float* floats, int cap, int* n);
+/* The sparse evaluation of the last Gaussian level (k_extrema_top's) at one point
+ * of the last extract: out[3 r + c] = the level at (x + c - 1, y + r - 1) of (image, octave),
+ * computed from the level below it; 1 <= x <= wa - 2, 1 <= y <= h - 2.  Stores nothing into the
+ * pyramid.  From the test-hook library, like sgpu_debug_candidates. */
+int sgpu_debug_top_level_at(sgpu_ctx* ctx, int image, int octave, int x, int y, float out[9]);
 
 /* Verified matches of many set pairs in one call: putative matching, one H and / or F per pair
  * with local refinement, and guided matching under those matrices, queued back to back on the

@@ -65,6 +65,10 @@ static void apply_env_hooks(sgpu_ctx* ctx) {
         if (!strcmp(ev, "end")) ctx->duo_plan = SGPU_PAIRS_END;
         if (!strcmp(ev, "front")) ctx->duo_plan = SGPU_PAIRS_FRONT;
     }
+    if (const char* ev = getenv("SGPU_TOP_LEVEL")) {   // A/B hook of the lazy top level
+        if (!strcmp(ev, "dense")) ctx->top_level = SGPU_TOP_LEVEL_DENSE;
+        if (!strcmp(ev, "lazy")) ctx->top_level = SGPU_TOP_LEVEL_LAZY;
+    }
     if (const char* ev = getenv("SGPU_TRIO")) {   // A/B hook of the three-level kernel
         if (!strcmp(ev, "off")) ctx->trio_mode = SGPU_TRIO_OFF;
         if (!strcmp(ev, "always")) ctx->trio_mode = SGPU_TRIO_ALWAYS;
@@ -416,6 +420,12 @@ int sgpu_debug_set_schedule(sgpu_ctx* ctx, int trio, int pairs) {
     return SGPU_OK;
 }
 
+int sgpu_debug_set_top_level(sgpu_ctx* ctx, int mode) {
+    if (!ctx || mode < SGPU_TOP_LEVEL_RULE || mode > SGPU_TOP_LEVEL_LAZY) return SGPU_EINVAL;
+    ctx->top_level = mode;
+    return SGPU_OK;
+}
+
 int sgpu_debug_geometry(const sgpu_ctx* ctx, int* n_octaves, int* dims, int max) {
     if (!ctx || !n_octaves) return SGPU_EINVAL;
     *n_octaves = (int)ctx->oct.size();
@@ -432,9 +442,17 @@ int sgpu_debug_gaussian(sgpu_ctx* ctx, int image, int octave, int level, float* 
         octave >= (int)ctx->oct.size() || level < 0 || level >= ctx->sched.level_num)
         return SGPU_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const Part& pt = ctx->part[ctx->part_of(image)];
+    Part& pt = ctx->part[ctx->part_of(image)];
     const sgk::OctaveDesc& od = pt.fp.oct[octave];
     const long long npx = (long long)od.wa * od.h;
+    if (level == ctx->sched.level_num - 1 && (size_t)octave < pt.top_dense.size() &&
+        !pt.top_dense[octave]) {
+        // a lazy pyramid holds this level only around its DoG candidates: filter it now (the
+        // sparse values are the same bits), dense until the next extract
+        HIPCHK(ctx, sgk::launch_gauss_op(pt.top_ops[octave], ctx->stream, 0));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        pt.top_dense[octave] = 1;
+    }
     const float* src = pt.pyr.as<float>() + od.gauss_off + level * od.level_stride +
                        (image - pt.img0) * npx;
     HIPCHK(ctx, hipMemcpy(out, src, npx * sizeof(float), hipMemcpyDeviceToHost));
@@ -443,20 +461,53 @@ int sgpu_debug_gaussian(sgpu_ctx* ctx, int image, int octave, int level, float* 
 
 // The test-hook library beside this one (lib/libsiftgpu_debug.so, csrc/sgpu_debug.hip), loaded on
 // first use: the candidate dump's kernel is not part of the product library.
-static sgk::DebugCandidatesFn debug_candidates_hook() {
-    static sgk::DebugCandidatesFn fn = [] {
+static void* debug_library() {
+    static void* lib = []() -> void* {
         Dl_info info{};
         if (!dladdr(reinterpret_cast<void*>(&sgpu_debug_candidates), &info) || !info.dli_fname)
-            return (sgk::DebugCandidatesFn) nullptr;
+            return nullptr;
         std::string path(info.dli_fname);
         const size_t slash = path.rfind('/');
         path = (slash == std::string::npos ? std::string(".") : path.substr(0, slash)) +
                "/libsiftgpu_debug.so";
-        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        return h ? reinterpret_cast<sgk::DebugCandidatesFn>(dlsym(h, "sgpu_testhook_candidates"))
-                 : (sgk::DebugCandidatesFn) nullptr;
+        return dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
     }();
+    return lib;
+}
+static void* debug_symbol(const char* name) {
+    void* h = debug_library();
+    return h ? dlsym(h, name) : nullptr;
+}
+static sgk::DebugCandidatesFn debug_candidates_hook() {
+    static sgk::DebugCandidatesFn fn =
+        reinterpret_cast<sgk::DebugCandidatesFn>(debug_symbol("sgpu_testhook_candidates"));
     return fn;
+}
+
+int sgpu_debug_top_level_at(sgpu_ctx* ctx, int image, int octave, int x, int y, float out[9]) {
+    if (!ctx || !out || image < 0 || image >= ctx->batch || ctx->img_off.empty() || octave < 0 ||
+        octave >= (int)ctx->oct.size())
+        return SGPU_EINVAL;
+    const Part& pt = ctx->part[ctx->part_of(image)];
+    const sgk::OctaveDesc& od = pt.fp.oct[octave];
+    if (x < 1 || x > od.wa - 2 || y < 1 || y > od.h - 2 || (size_t)octave >= pt.top_ops.size())
+        return ctx->fail(SGPU_EINVAL, "point outside the octave's interior");
+    const sgk::DebugTopLevelFn hook = reinterpret_cast<sgk::DebugTopLevelFn>(debug_symbol("sgpu_testhook_top_level"));
+    if (!hook) return ctx->fail(SGPU_EINVAL, "test-hook library lib/libsiftgpu_debug.so not found");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf d;
+    ALLOCCHK(ctx, d.ensure(9 * sizeof(float)));
+    sgk::TopLevelFilter tf;
+    tf.fw = pt.top_ops[octave].fw;
+    tf.taps = pt.top_ops[octave].taps;
+    hipError_t e = hook(pt.pyr.as<float>(), &pt.fp, &tf, image - pt.img0, octave, x, y,
+                        d.as<float>(), ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, d.p, 9 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    d.release();
+    HIPCHK(ctx, e);
+    return SGPU_OK;
 }
 
 int sgpu_debug_candidates(sgpu_ctx* ctx, int* ints, float* floats, int cap, int* n) {

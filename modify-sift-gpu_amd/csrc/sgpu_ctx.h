@@ -81,6 +81,13 @@ struct Part {
     std::vector<sgk::LevelOp> ops;
     std::vector<sgpyr::LevelDesc> levels;
     sgpyr::Plan plan;
+    // the octaves' last level: its filter per octave, kept beside the list; lazy =
+    // the last pyramid left it out (the extremum pass evaluated it at the pending pixels only);
+    // top_dense[o] = octave o's plane holds the whole level (always unless lazy; in a lazy part
+    // once sgpu_debug_gaussian has filled it in)
+    std::vector<sgk::LevelOp> top_ops;
+    std::vector<char> top_dense;
+    bool lazy = false;
     bool events = true;                    // the last enqueue recorded its stage events
     bool copied_out = false;               // the last enqueue copied its results to host_out
     hipEvent_t ev[10] = {};  // start, pyramid, detect, orientation, expand, descriptor, end,
@@ -140,6 +147,9 @@ struct sgpu_ctx {
                                            // always; sgpu_debug_set_schedule)
     int duo_plan = SGK_DUO_PLAN;           // SGPU_PAIRS_END: pairs from the octave's end
                                            // (SGPU_DUO_PLAN=end), SGPU_PAIRS_FRONT: from its front
+    int top_level = SGPU_TOP_LEVEL_RULE;   // the octaves' last Gaussian level: dense, or only around
+                                           // its DoG candidates (SGPU_TOP_LEVEL=dense|lazy;
+                                           // sgpu_debug_set_top_level)
     int duo_strips = SGPU_DUO_STRIPS_RULE; // strip geometry of the paired-level launches
                                            // (sgpu_debug_set_duo_strips)
     size_t wide_desc_max = SGK_WIDE_DESC_MAX;   // feature counts (of the previous call) up to which

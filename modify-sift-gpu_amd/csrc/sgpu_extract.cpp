@@ -115,9 +115,11 @@ static int layout_part(sgpu_ctx* ctx, Part& pt) {
 // of them into pt.levels: op (o, k) filters level k-1 into level k (op (0, 0) smooths the input
 // into level 0); level kds = level_ds - level_min of octave o also writes its 2x decimation as
 // level 0 of octave o+1 (PyramidCU.cpp:1024).  With -fo != 0 it first queues the input's
-// resampling on st.
+// resampling on st.  The filter of every octave's last level is also kept in pt.top_ops; with
+// `lazy` it is left out of the list (nothing but the last DoG plane reads that
+// level, and the extremum pass evaluates it where a candidate needs it).
 static int build_level_ops(sgpu_ctx* ctx, Part& pt, const uint8_t* src8, const float* srcf,
-                           int stride, hipStream_t st) {
+                           int stride, hipStream_t st, bool lazy) {
     const sgpu_options& O = ctx->opt;
     const sgp::Schedule& S = ctx->sched;
     const sgk::FeatureParams& fp = pt.fp;
@@ -134,6 +136,7 @@ static int build_level_ops(sgpu_ctx* ctx, Part& pt, const uint8_t* src8, const f
     pt.levels.clear();
     pt.ops.reserve((size_t)noct * nlev);
     pt.levels.reserve((size_t)noct * nlev);
+    pt.top_ops.resize((size_t)noct);
     for (int o = 0; o < noct; o++) {
         const sgk::OctaveDesc& od = fp.oct[o];
         const long long npx = (long long)od.wa * od.h;
@@ -193,6 +196,13 @@ static int build_level_ops(sgpu_ctx* ctx, Part& pt, const uint8_t* src8, const f
                 op.zero.n[1] = (size_t)pt.mask_words;
                 op.zero.p[2] = pt.ocount.as<uint32_t>();
                 op.zero.n[2] = sgk::feature_queue_base(pt.cand_cap) + sgk::kFeatureQueueWords;   // + the work counters
+            }
+            if (k == nlev - 1) {
+                pt.top_ops[o] = op;
+                if (lazy) {
+                    pt.ops.pop_back();
+                    continue;
+                }
             }
             pt.levels.push_back(sgpyr::LevelDesc{o, k, op.fw, op.w, op.h, op.batch, dk,
                                                  op.src_u8 != nullptr,
@@ -278,7 +288,17 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
     // filters, the planner's launch list for them (sift_pyramid_plan.h: every schedule decision
     // is made there), and one launch per entry.
     float* pyr = pt.pyr.as<float>();
-    const int rc_ops = build_level_ops(ctx, pt, src8, srcf, stride, st);
+    // a cache-resident pyramid (the same size rule as the level tiles): the tile extremum kernel
+    const bool ext_small = 4ll * fp.oct[0].wa * fp.oct[0].h * n <= ((long long)ctx->tile_mb << 20);
+    const bool ext_tiles = !(ctx->debug_flags & SGPU_DEBUG_EXTREMA_TILE_OFF) &&
+                           ((ctx->debug_flags & SGPU_DEBUG_GAUSS_TILE_ALWAYS) || ext_small);
+    // The octaves' last level is left out where the wave-streaming extremum kernel
+    // runs because the size rule chose it (SGPU_TOP_LEVEL_RULE, shipped), or wherever it runs
+    // (SGPU_TOP_LEVEL_LAZY); the tile extremum kernel always gets the dense pyramid.
+    pt.lazy = !ext_tiles && ctx->top_level != SGPU_TOP_LEVEL_DENSE &&
+              (ctx->top_level == SGPU_TOP_LEVEL_LAZY || !ext_small);
+    pt.top_dense.assign(ctx->oct.size(), pt.lazy ? 0 : 1);
+    const int rc_ops = build_level_ops(ctx, pt, src8, srcf, stride, st, pt.lazy);
     if (rc_ops != SGPU_OK) return rc_ops;
     const sgpyr::Rules R = pyramid_rules(ctx, pt);
     sgpyr::plan_pyramid(pt.levels.data(), (int)pt.levels.size(), R, OpSupport{pt.ops.data()}, pt.plan);
@@ -323,12 +343,15 @@ static int enqueue_part(sgpu_ctx* ctx, Part& pt, const void* src_in, bool is_f32
     if (!pt.one_stream)
         HIPCHK(ctx, sgk::launch_zero(pt.row_count.as<uint32_t>(), (size_t)pt.total_rows,
                                      pt.mask.as<uint32_t>(), (size_t)moff, nullptr, 0, st));
-    // a cache-resident pyramid (the same size rule as the level tiles): the tile extremum kernel
-    const bool ext_tiles = !(ctx->debug_flags & SGPU_DEBUG_EXTREMA_TILE_OFF) &&
-                           ((ctx->debug_flags & SGPU_DEBUG_GAUSS_TILE_ALWAYS) ||
-                            4ll * fp.oct[0].wa * fp.oct[0].h * n <= ((long long)ctx->tile_mb << 20));
     HIPCHK(ctx, sgk::launch_extrema(pyr, pt.mask.as<uint32_t>(), pt.row_count.as<uint32_t>(),
-                                    fp, st, ext_tiles));
+                                    fp, st, ext_tiles, pt.lazy));
+    if (pt.lazy) {   // the pending pixels of the top DoG level: evaluate, test, count or clear
+        sgk::TopLevelFilter tf;
+        tf.fw = pt.top_ops[0].fw;
+        tf.taps = pt.top_ops[0].taps;
+        HIPCHK(ctx, sgk::launch_extrema_top(pyr, pt.mask.as<uint32_t>(), pt.row_count.as<uint32_t>(),
+                                            fp, tf, st));
+    }
     if (O.feature_count_threshold > 0)   // -tc: GenerateFeatureList skip + LimitFeatureCount(0)
         HIPCHK(ctx, sgk::launch_limit_rows(pt.row_count.as<uint32_t>(), fp,
                                            O.feature_count_threshold, O.truncate_method, st));

@@ -12,6 +12,7 @@
 
 #include "sift_device.h"
 #include "sift_keys.h"
+#include "sift_top_level.h"
 
 // Build-time tuning knobs (tests/build_variant.sh passes -D overrides; the values here ship).
 #ifndef SGK_EXT2_WAVES
@@ -74,7 +75,13 @@ struct ExtremaWaveGrid {
 // load per plane and row instead of two 4-byte ones: the texture-address unit, ~88 % busy with
 // 4-byte loads, handles a load per lane whatever its width), 126 tested columns per wave;
 // x0 = 126 sx + 1 keeps the pairs 8-byte aligned.
-template <int ND, int CPL>   // ND = number of DoG planes = d + 2
+// LAZY: the octave's last Gaussian level was not filtered.  The wave fetches planes
+// 0 .. nlev-2 and forms ND - 1 DoG rows; DoG levels j < d-1 are decided as always; for j = d-1 the
+// pre-filter runs over the 18 values of the two planes it has (a superset of the 27-value one:
+// a maximum over fewer values is no larger), ComputeKEY runs up to its last previous-plane row
+// (key_test<true>), and a pixel it has not rejected by then gets its mask bit without a row count:
+// k_extrema_top decides it.
+template <int ND, int CPL, bool LAZY = false>   // ND = number of DoG planes = d + 2
 __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const float* __restrict__ pyr,
                                                        uint32_t* __restrict__ mask,
                                                        uint32_t* __restrict__ row_count,
@@ -84,7 +91,8 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
     constexpr int TW = 64 * CPL - 2;                // tested columns per wave
     constexpr int RW = 64 * CPL + 2 * CPL + 2;      // ring row: column index i at i + CPL (+pad)
     constexpr int NJ = ND - 2;
-    __shared__ __attribute__((aligned(8))) float s_ring[4][ND][4][RW];   // [wave][plane][row & 3][col]
+    constexpr int NR = LAZY ? ND - 1 : ND;          // DoG rows formed (NR + 1 Gaussian planes read)
+    __shared__ __attribute__((aligned(8))) float s_ring[4][NR][4][RW];   // [wave][plane][row & 3][col]
     __shared__ uint16_t s_list[4][NJ * 64 * CPL];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Workgroup order.  Two neighbouring 128-column windows (126 columns apart, not line-aligned)
@@ -132,12 +140,12 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
         const int i = CPL * lane + k, x = xl + k;
         out_col[k] = i >= 1 && i <= TW && x > 0 && x < W - 1;
     }
-    struct Row { float m[ND + 1][CPL]; };
+    struct Row { float m[NR + 1][CPL]; };
     Row rA, rB;
     auto fetch = [&](Row& r, int y) {   // G row y (clamped) into registers
         const float* q = g0 + (long long)clampi(y, 0, H - 1) * W + gx;
 #pragma unroll
-        for (int m = 0; m <= ND; m++) {
+        for (int m = 0; m <= NR; m++) {
             if constexpr (CPL == 1) {
                 r.m[m][0] = q[m * lstride];
             } else {
@@ -153,11 +161,11 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
     // every write before the reads that follow it.
     // DoG row y into the ring (read by key_test for the rare candidates) and into dog[] (the
     // row max/min below take the neighbours' values by DPP wave shifts, not from LDS)
-    float dog[ND][CPL];
+    float dog[NR][CPL];
     auto put = [&](const Row& r, int y) {
         float* rr = &ring[0][y & 3][CPL * lane + CPL];
 #pragma unroll
-        for (int m = 0; m < ND; m++) {
+        for (int m = 0; m < NR; m++) {
 #pragma unroll
             for (int k = 0; k < CPL; k++) dog[m][k] = r.m[m + 1][k] - r.m[m][k];
             if constexpr (CPL == 1)
@@ -170,10 +178,10 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
     // rolling 3-wide row max/min of DoG rows y-1 and y (per plane), refreshed per step; the
     // wave's first and last columns get a neighbour from outside the wave (0) and are never
     // tested
-    float hx0[ND][CPL], hn0[ND][CPL], hx1[ND][CPL], hn1[ND][CPL], cvx[ND][CPL];
+    float hx0[NR][CPL], hn0[NR][CPL], hx1[NR][CPL], hn1[NR][CPL], cvx[NR][CPL];
     auto rowmm = [&](float (*mx)[CPL], float (*mn)[CPL], float (*cv)[CPL]) {   // of dog[]
 #pragma unroll
-        for (int m = 0; m < ND; m++) {
+        for (int m = 0; m < NR; m++) {
             float v[CPL + 2];   // columns left of, in and right of this lane's
 #pragma unroll
             for (int k = 0; k < CPL; k++) v[k + 1] = dog[m][k];
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
         }
     };
     auto body = [&](int y) {   // test row y: DoG rows y-1, y are rolled, y+1 is in dog[]
-        float hx2[ND][CPL], hn2[ND][CPL], cnx[ND][CPL];
+        float hx2[NR][CPL], hn2[NR][CPL], cnx[NR][CPL];
         rowmm(hx2, hn2, cnx);
         const bool row_ok = y < ye && y > 0 && y < H - 1;
         int ncand = 0;
@@ -201,7 +209,7 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
                 const float v = cvx[j + 1][k];
                 float mx = hx0[j][k], mn = hn0[j][k];
 #pragma unroll
-                for (int m = j; m < j + 3; m++) {
+                for (int m = j; m < j + 3 && m < NR; m++) {
                     mx = fmax_(mx, fmax_(fmax_(hx0[m][k], hx1[m][k]), hx2[m][k]));
                     mn = fmin_(mn, fmin_(fmin_(hn0[m][k], hn1[m][k]), hn2[m][k]));
                 }
@@ -227,10 +235,13 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
                 auto get = [&](int m, int r, int c) {
                     return ring[j + m][(y + r - 1) & 3][cl + c - 1 + CPL];
                 };
-                if (key_test(get, fp.t0, fp.t, fp.edge, fp.subpixel).result != 0.f) {
-                    const int xx = x0 - 1 + cl;
-                    uint32_t* mrow = mask + mask_off + j * mask_lstride +
-                                     ((long long)b * H + y) * nwords;
+                const int xx = x0 - 1 + cl;
+                uint32_t* mrow = mask + mask_off + j * mask_lstride + ((long long)b * H + y) * nwords;
+                if (LAZY && j == NJ - 1) {
+                    // pending: the bit alone (no list, no counter; k_extrema_top walks the mask)
+                    if (key_test<true>(get, fp.t0, fp.t, fp.edge, fp.subpixel).result != 0.f)
+                        atomicOr(&mrow[xx >> 5], 1u << (xx & 31));
+                } else if (key_test(get, fp.t0, fp.t, fp.edge, fp.subpixel).result != 0.f) {
                     atomicOr(&mrow[xx >> 5], 1u << (xx & 31));
                     atomicAdd(&row_count[(long long)b * fp.rows_per_image + rc_base + j * H + y],
                               1u);
@@ -238,7 +249,7 @@ __global__ __launch_bounds__(256, SGK_EXT2_WAVES) void k_extrema_wave2(const flo
             }
         }
 #pragma unroll
-        for (int m = 0; m < ND; m++)
+        for (int m = 0; m < NR; m++)
 #pragma unroll
             for (int k = 0; k < CPL; k++) {
                 hx0[m][k] = hx1[m][k]; hn0[m][k] = hn1[m][k];
@@ -387,6 +398,128 @@ __global__ __launch_bounds__(256) void k_extrema_tile(const float* __restrict__ 
                                  ((long long)b * H + y) * od.nwords;
                 atomicOr(&mrow[x >> 5], 1u << (x & 31));
                 atomicAdd(&row_count[(long long)b * fp.rows_per_image + fp.row_off[o] + j * H + y], 1u);
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The pending pixels of the lazy extremum pass.  A unit is kTopRows consecutive
+// rows of DoG level d-1's mask region of one octave (rows ordered image, row); waves take units
+// by a static grid stride.  A wave loads its unit's mask words at once (a lane per word and row),
+// then in rounds: every lane hands in the lowest set bit of each of its words, compacted into a
+// wave-private list (ballot + mbcnt), and the wave works through the list with all 64 lanes per
+// pixel.  Per pixel: the (fw+2)^2 window of level nlev-2 and the 3 x 3 of planes nlev-4 .. nlev-2
+// are loaded one pixel ahead (the loads of pixel i+1 are in flight while pixel i is computed: the
+// windows come from HBM, ~2 us away); top_level_eval gives level nlev-1 at the nine points, which
+// are stored into the level's plane (neighbouring pending pixels store equal bits to shared
+// points; nobody reads the plane in this kernel); lane 0 runs the exact ComputeKEY test with the
+// last DoG plane formed from the fresh values in LDS.  Accepted: the row count; rejected: the bit
+// is cleared.  A mask word belongs to one wave, bits and counts do not depend on the order, so
+// mask, counts and everything after them are the dense path's.
+constexpr int kTopRows = 8;
+struct ExtremaTopGrid {
+    int unit0[kMaxOctaves + 1];   // first unit of octave o
+};
+
+template <int FW>
+__global__ __launch_bounds__(256) void k_extrema_top(float* __restrict__ pyr,
+                                                     uint32_t* __restrict__ mask,
+                                                     uint32_t* __restrict__ row_count,
+                                                     const FeatureParams fp, const ExtremaTopGrid tg,
+                                                     const TopLevelFilter tf) {
+    using G = TopGeom<FW>;
+    __shared__ TopLds s_all[4];
+    __shared__ uint16_t s_list[4][kTopRows * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    TopLds& s = s_all[wave];
+    uint16_t* list = s_list[wave];
+    const int jt = fp.d - 1, top = fp.d + 2;   // top = nlev - 1
+    const int nwaves = gridDim.x * 4;
+    const int gm = lane / 9, gq = lane - 9 * gm, gr = gq / 3, gc = gq - 3 * gr;   // lanes < 27: plane, row, column
+    for (int u = blockIdx.x * 4 + wave; u < tg.unit0[fp.n_octaves]; u += nwaves) {
+        int o = 0;
+        while (o + 1 < fp.n_octaves && u >= tg.unit0[o + 1]) o++;
+        o = __builtin_amdgcn_readfirstlane(o);
+        const OctaveDesc& od = fp.oct[o];
+        const int W = od.wa, H = od.h, nwords = od.nwords;
+        const long long npx = (long long)W * H, lstride = od.level_stride;
+        const long long rows = (long long)fp.batch * H;       // rows of the level's mask region
+        const long long r0 = (long long)(u - tg.unit0[o]) * kTopRows;
+        const int b0 = (int)(r0 / H), y0 = (int)(r0 - (long long)b0 * H);
+        uint32_t* mtop = mask + od.mask_off + jt * od.mask_level_stride;
+        float* g0 = pyr + od.gauss_off;   // level 0, image 0
+        // (image, row) of a list entry's row k, its plane pointers, and the entry's loads
+        struct Px { int b, y, x, k; };
+        auto locate_px = [&](int code) {
+            Px p;
+            p.k = code >> 12;
+            p.x = code & 4095;
+            p.b = b0;
+            p.y = y0 + p.k;
+            while (p.y >= H) { p.y -= H; p.b++; }
+            return p;
+        };
+        for (int w0 = 0; w0 < nwords; w0 += 64) {
+            uint32_t word[kTopRows];
+#pragma unroll
+            for (int k = 0; k < kTopRows; k++)
+                word[k] = (r0 + k < rows && w0 + lane < nwords) ? mtop[(r0 + k) * nwords + w0 + lane] : 0u;
+            for (;;) {
+                int cnt = 0;
+#pragma unroll
+                for (int k = 0; k < kTopRows; k++) {
+                    const bool has = word[k] != 0u;
+                    const unsigned long long bal = __ballot(has);
+                    if (has) {
+                        const int bit = __ffs(word[k]) - 1;
+                        word[k] &= word[k] - 1;
+                        const int pos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                        list[pos] = (uint16_t)((k << 12) | (lane * 32 + bit));
+                    }
+                    cnt += __popcll(bal);
+                }
+                if (cnt == 0) break;
+                asm volatile("" ::: "memory");
+                float vc[G::NLD], vn[G::NLD], gvc, gvn;
+                auto fetch = [&](int i, float (&v)[G::NLD], float& gv) {
+                    const Px p = locate_px(__builtin_amdgcn_readfirstlane((int)list[i]));
+                    const int x = w0 * 32 + p.x;
+                    const float* g = g0 + (long long)p.b * npx;
+                    top_window_load<FW>(g + (top - 1) * lstride, W, H, x, p.y, lane, v);
+                    // planes nlev-4 .. nlev-2 around the pixel (clamped: only interior bits are
+                    // ever set, and no address leaves the plane whatever the mask holds)
+                    const int yy = top_clamp(p.y + gr - 1, 0, H - 1), xx = top_clamp(x + gc - 1, 0, W - 1);
+                    gv = g[(top - 3 + min(gm, 2)) * lstride + (uint32_t)(yy * W + xx)];
+                };
+                fetch(0, vc, gvc);
+                for (int i = 0; i < cnt; i++) {
+                    fetch(min(i + 1, cnt - 1), vn, gvn);   // (the last round re-reads its own lines)
+                    const Px p = locate_px(__builtin_amdgcn_readfirstlane((int)list[i]));
+                    const int x = w0 * 32 + p.x, y = p.y;
+                    const bool interior = x >= 1 && x <= W - 2 && y >= 1 && y <= H - 2;
+                    if (lane < 27) s.g[lane] = gvc;
+                    top_level_eval<FW>(vc, tf.taps, s, lane);
+                    float* g = g0 + (long long)p.b * npx;
+                    if (lane < 9 && interior)
+                        g[top * lstride + (long long)(y + gr - 1) * W + x + gc - 1] = s.top[lane];
+                    if (lane == 0) {
+                        auto get = [&](int m, int r, int c) {
+                            const int q = 3 * r + c;
+                            return (m == 2 ? s.top[q] : s.g[9 * (m + 1) + q]) - s.g[9 * m + q];
+                        };
+                        if (interior && key_test(get, fp.t0, fp.t, fp.edge, fp.subpixel).result != 0.f)
+                            atomicAdd(&row_count[(long long)p.b * fp.rows_per_image + fp.row_off[o] + jt * H + y], 1u);
+                        else
+                            atomicAnd(&mtop[(r0 + p.k) * nwords + w0 + (p.x >> 5)], ~(1u << (p.x & 31)));
+                    }
+                    asm volatile("" ::: "memory");   // this pixel's LDS reads before the next one's writes
+#pragma unroll
+                    for (int q = 0; q < G::NLD; q++) vc[q] = vn[q];
+                    gvc = gvn;
+                }
             }
         }
     }
@@ -580,7 +713,8 @@ __global__ __launch_bounds__(256) void k_limit_oriented(uint32_t* __restrict__ o
 
 // ------------------------------------------------------------------------------------------
 hipError_t launch_extrema(const float* pyr, uint32_t* mask, uint32_t* row_count,
-                          const FeatureParams& fp, hipStream_t stream, bool tiles) {
+                          const FeatureParams& fp, hipStream_t stream, bool tiles, bool lazy) {
+    if (tiles && lazy) return hipErrorInvalidValue;   // the tile kernel reads every plane
     bool tile_ok = tiles && ((uintptr_t)pyr % 16) == 0;
     for (int o = 0; o < fp.n_octaves; o++)
         tile_ok = tile_ok && fp.oct[o].wa % 4 == 0 && fp.oct[o].wa >= 4 && fp.oct[o].gauss_off % 4 == 0 &&
@@ -640,17 +774,58 @@ hipError_t launch_extrema(const float* pyr, uint32_t* mask, uint32_t* row_count,
     }
     eg.wave0[fp.n_octaves] = nw;
     const unsigned nb = (unsigned)((nw + 3) / 4);
-    switch ((fp.d + 2) * 2 + (pairs ? 1 : 0)) {
-#define SGK_EXTW(ND)                                                                             \
-    case 2 * ND: hipLaunchKernelGGL((k_extrema_wave2<ND, 1>), dim3(nb), dim3(256), 0, stream, pyr, \
-                                    mask, row_count, fp, eg); break;                             \
-    case 2 * ND + 1: hipLaunchKernelGGL((k_extrema_wave2<ND, 2>), dim3(nb), dim3(256), 0, stream,  \
-                                        pyr, mask, row_count, fp, eg); break;
-        SGK_EXTW(3) SGK_EXTW(4) SGK_EXTW(5) SGK_EXTW(6) SGK_EXTW(7) SGK_EXTW(8)
-        default: return hipErrorInvalidValue;
-#undef SGK_EXTW
+#define SGK_EXTW(ND, LAZY)                                                                       \
+    case 2 * ND: hipLaunchKernelGGL((k_extrema_wave2<ND, 1, LAZY>), dim3(nb), dim3(256), 0, stream, \
+                                    pyr, mask, row_count, fp, eg); break;                        \
+    case 2 * ND + 1: hipLaunchKernelGGL((k_extrema_wave2<ND, 2, LAZY>), dim3(nb), dim3(256), 0,    \
+                                        stream, pyr, mask, row_count, fp, eg); break;
+    if (lazy) {
+        switch ((fp.d + 2) * 2 + (pairs ? 1 : 0)) {
+            SGK_EXTW(3, true) SGK_EXTW(4, true) SGK_EXTW(5, true) SGK_EXTW(6, true)
+            SGK_EXTW(7, true) SGK_EXTW(8, true)
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch ((fp.d + 2) * 2 + (pairs ? 1 : 0)) {
+            SGK_EXTW(3, false) SGK_EXTW(4, false) SGK_EXTW(5, false) SGK_EXTW(6, false)
+            SGK_EXTW(7, false) SGK_EXTW(8, false)
+            default: return hipErrorInvalidValue;
+        }
     }
+#undef SGK_EXTW
     return hipGetLastError();
+}
+
+hipError_t launch_extrema_top(float* pyr, uint32_t* mask, uint32_t* row_count,
+                              const FeatureParams& fp, const TopLevelFilter& tf,
+                              hipStream_t stream) {
+    if (tf.fw < 1 || tf.fw > kTopMaxFW || !(tf.fw & 1) || fp.d < 1) return hipErrorInvalidValue;
+    ExtremaTopGrid tg{};
+    long long nu = 0;
+    for (int o = 0; o < fp.n_octaves; o++) {
+        tg.unit0[o] = (int)nu;
+        nu += ((long long)fp.batch * fp.oct[o].h + kTopRows - 1) / kTopRows;
+    }
+    if (nu <= 0 || nu >= (1ll << 31)) return hipErrorInvalidValue;
+    tg.unit0[fp.n_octaves] = (int)nu;
+    // a resident grid (static stride: workgroups that start after the first residents would only
+    // lengthen the tail)
+    int dev = 0, cus = 0, per_cu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    const bool known = top_level_dispatch(tf.fw, [&](auto FWC) {
+        constexpr int FW = decltype(FWC)::value;
+        static int resident = 0;   // per width; the same for every device of one kind
+        if (!resident &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, k_extrema_top<FW>, 256, 0) != hipSuccess)
+            resident = 0;
+        per_cu = std::max(1, resident);
+        const unsigned nb = (unsigned)std::min<long long>((nu + 3) / 4, (long long)std::max(1, cus) * per_cu);
+        hipLaunchKernelGGL((k_extrema_top<FW>), dim3(nb), dim3(256), 0, stream, pyr, mask, row_count,
+                           fp, tg, tf);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 static size_t scan_blocks(size_t n) { return (n + 1023) / 1024; }

@@ -12,6 +12,10 @@
 //   * DoG and gradient images are never stored: the extremum kernel forms the 5 DoG planes of
 //     an octave in LDS from the 6 Gaussian planes, and the orientation / descriptor kernels
 //     evaluate gradients from the Gaussian level on the fly;
+//   * the octaves' last Gaussian level is a leaf (only the last DoG plane reads it): a streaming
+//     batch does not filter it, k_extrema_top evaluates it at the 3 x 3 neighbourhoods of the top
+//     DoG level's undecided pixels, and the rest of that level's plane holds stale data
+//     (launch_extrema / launch_extrema_top);
 //   * keypoint compaction is a 1-bit-per-pixel mask written with wave ballots plus per-row
 //     counts; one exclusive scan over rows gives every keypoint its slot in the reference's
 //     (image, octave, level, row, column) order -- no histogram pyramid, no host round trips.
@@ -171,8 +175,27 @@ hipError_t launch_color_to_gray(const uint8_t* src, int n, int w, int h, int str
 // (rows ordered image, octave, level, row).  tiles: the 2-D tile kernel (k_extrema_tile: each
 // workgroup loads its 64 x 16-pixel window of every plane at once; for cache-resident pyramids),
 // else the wave-streaming k_extrema_wave2 -- the same bits and counts.
+// lazy (wave kernel only): the pyramid's last level of every octave was not
+// filtered and holds stale data.  The kernel then reads planes 0 .. nlev-2 only, decides DoG levels
+// 0 .. d-2 as always, and for DoG level d-1 sets the mask bit -- without counting it -- of every
+// pixel that ComputeKEY does not reject before it reads the last DoG plane; launch_extrema_top
+// must follow.
 hipError_t launch_extrema(const float* pyr, uint32_t* mask, uint32_t* row_count,
-                          const FeatureParams& fp, hipStream_t stream, bool tiles = false);
+                          const FeatureParams& fp, hipStream_t stream, bool tiles = false,
+                          bool lazy = false);
+// The filter that writes an octave's last level (the same taps in every octave).
+struct TopLevelFilter {
+    int fw;
+    Taps taps;
+};
+// Finishes the pending pixels of launch_extrema(lazy): for every set bit of DoG level d-1's mask
+// region it evaluates the last Gaussian level at the pixel's 3 x 3 neighbourhood (the dense
+// kernels' bits), stores the nine values into that level's plane -- the rest of the plane stays
+// stale -- and runs the exact ComputeKEY test: an accepted pixel counts in its row, a rejected one
+// has its bit cleared.  Mask and counts are then what the dense path leaves.
+hipError_t launch_extrema_top(float* pyr, uint32_t* mask, uint32_t* row_count,
+                              const FeatureParams& fp, const TopLevelFilter& tf,
+                              hipStream_t stream);
 
 // Exclusive scan of n uint32 values into out[0..n]; out[n] = total.  tmp needs
 // scan_tmp_words(n) words.
@@ -297,6 +320,12 @@ typedef hipError_t (*DebugCandidatesFn)(const float* pyr, const uint32_t* mask,
                                         const uint32_t* n_cand_dev, int n_cand_cap,
                                         const FeatureParams* fp, int4* ints, float4* floats,
                                         hipStream_t stream);
+// The same library's one-point probe of the sparse top-level evaluation (sift_top_level.h): the
+// nine values of level nlev-1 around (x, y) of (image, octave) into out9 (device), computed from
+// level nlev-2 as k_extrema_top computes them; nothing is stored into the pyramid.
+typedef hipError_t (*DebugTopLevelFn)(const float* pyr, const FeatureParams* fp,
+                                      const TopLevelFilter* tf, int image, int octave, int x, int y,
+                                      float* out9, hipStream_t stream);
 
 // ---- matcher (sift_match.hip) ----
 // Distance table dist[v] = float(acos(min(v * 2^-18, 1.0))) for v in [0, 262144], built on the

@@ -14,7 +14,12 @@ namespace {
 // decides ties.
 struct KeyOut { float result, dx, dy, ds; };
 
-template <class Get>
+// UNTIL_NEXT: stop before the first read of the next DoG level, get(2, ., .), and report
+// result = kKeyUndecided for a pixel that no earlier step rejected (the lazy extremum pass,
+// the next plane does not exist yet).
+constexpr float kKeyUndecided = 2.0f;
+
+template <bool UNTIL_NEXT = false, class Get>
 __device__ __forceinline__ KeyOut key_test(Get get, float t0, float t, float edge, int subpixel) {
     KeyOut o{0.f, 0.f, 0.f, 0.f};
     const float v = get(1, 1, 1);
@@ -27,6 +32,10 @@ __device__ __forceinline__ KeyOut key_test(Get get, float t0, float t, float edg
     const int seq_r[8] = {0, 2, 0, 1, 2, 0, 1, 2};
 #pragma unroll
     for (int s = 0; s < 8; s++) {
+        if (UNTIL_NEXT && s == 5) {
+            o.result = kKeyUndecided;
+            return o;
+        }
         if (s == 2) {
             const float vx2 = v * 2.0f;
             const float fxx = l + r - vx2;

@@ -43,6 +43,7 @@ C_API = [
     "sgpu_default_verify_params", "sgpu_verify_batch", "sgpu_verify_images",
     "sgpu_select_top_scale_batch", "sgpu_select_top_scale_images",
     "sgpu_prematch_batch", "sgpu_prematch_images",
+    "sgpu_debug_set_top_level", "sgpu_debug_top_level_at",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -97,6 +98,8 @@ def lib():
         L.sgpu_debug_set_match_prune.argtypes = [vp, c.c_int]
         L.sgpu_debug_set_duo_strips.argtypes = [vp, c.c_int]
         L.sgpu_debug_set_feature_queue.argtypes = [vp, c.c_int]
+        L.sgpu_debug_set_top_level.argtypes = [vp, c.c_int]
+        L.sgpu_debug_top_level_at.argtypes = [vp, c.c_int, c.c_int, c.c_int, c.c_int, vp]
         L.sgpu_debug_geometry.argtypes = [vp, P(c.c_int), vp, c.c_int]
         L.sgpu_debug_gaussian.argtypes = [vp, c.c_int, c.c_int, c.c_int, vp]
         L.sgpu_debug_candidates.argtypes = [vp, vp, vp, c.c_int, P(c.c_int)]
@@ -1098,6 +1101,23 @@ class SiftContext:
         lane-columns and measured faster), STRIPS_WAVE (a 96-column strip per wave everywhere),
         STRIPS_COOP (the shared strip wherever it is compiled, at any width): the same levels."""
         self._check(lib().sgpu_debug_set_duo_strips(self._ctx, mode), "sgpu_debug_set_duo_strips")
+
+    TOP_LEVEL_RULE, TOP_LEVEL_DENSE, TOP_LEVEL_LAZY = 0, 1, 2
+
+    def set_top_level(self, mode: int = 0):
+        """Every octave's last Gaussian level (sgpu_debug_set_top_level): TOP_LEVEL_DENSE (filtered
+        for every pixel), TOP_LEVEL_LAZY (evaluated only around the top DoG level's candidates,
+        wherever the wave-streaming extremum kernel runs) or TOP_LEVEL_RULE (shipped: lazy for
+        batches too large for the tile extremum kernel): the same features."""
+        self._check(lib().sgpu_debug_set_top_level(self._ctx, mode), "sgpu_debug_set_top_level")
+
+    def top_level_at(self, image, octave, x, y):
+        """The last Gaussian level's 3 x 3 values around (x, y) of (image, octave) by the sparse
+        evaluation (sgpu_debug_top_level_at): a (3, 3) float32 array, [row, column]."""
+        out = np.zeros(9, np.float32)
+        self._check(lib().sgpu_debug_top_level_at(self._ctx, image, octave, x, y, out.ctypes.data),
+                    "sgpu_debug_top_level_at")
+        return out.reshape(3, 3)
 
     FEATURES_QUEUE, FEATURES_STATIC_ORIENTATION, FEATURES_STATIC_DESCRIPTOR, FEATURES_STATIC = 0, 1, 2, 3
 
