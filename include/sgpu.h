@@ -386,7 +386,7 @@ int sgpu_estimate_images_refined(sgpu_ctx* ctx, const int* image_pairs, int npai
  * extract; times[8] = the last sgpu_match call; times[9] = the feature-list (row scan) part of
  * detect; times[10], [11] = the key and descriptor copies of the last sgpu_copy_features;
  * times[12] = the last sgpu_estimate_* call; times[13] = the last sgpu_verify_* call; times[14] =
- * the last sgpu_prematch_* call.
+ * the last sgpu_prematch_* call; times[15] = the last sgpu_tracks_* call.
  * SiftGPU::_timing[2..8] map them to the reference's slots (siftgpu_api.cpp).  Slots 0-7 and
  * 9-11 read 0 after a one-stream extract / copy made with the stage timing off. */
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n);
@@ -688,6 +688,53 @@ int sgpu_prematch_batch(sgpu_ctx* ctx, const uint8_t* desc, const float* scale, 
 int sgpu_prematch_images(sgpu_ctx* ctx, const int* image_pairs, int npairs, int top,
                          float distmax, float ratiomax, int mutual_best_match,
                          int* out_counts, int* out_pairs, int64_t cap);
+
+/* Feature tracks from a pair list's matches, built on the device: the step between matching and
+ * reconstruction (Wu, 3DV 2013).  A track is the set of features, at most one per set, that the
+ * matches connect transitively.  No reference counterpart in SiftGPU.
+ *
+ * Rule (csrc/sift_tracks.h).  set_offsets, set_pairs, matches (set-local {i, j},
+ * concatenated in pair order) and match_counts are the offsets, pair list, out_pairs and out_counts
+ * of sgpu_match_batch, sgpu_match_batch_guided or sgpu_verify_batch.  A node is a buffer row
+ * r = set_offsets[s] + i, rows = set_offsets[nsets]; match {i, j} of pair (a, b) is the edge
+ * (set_offsets[a] + i, set_offsets[b] + j), a self-loop is none.  A connected component is
+ * labelled by its smallest row.  With fewer than min_length rows it is short; otherwise, with more
+ * rows than nsets or two rows in one set, inconsistent; otherwise a track.  Tracks are numbered
+ * 0 .. T - 1 in ascending label order.
+ *   out_track [rows]          the row's track id; SGPU_TRACK_NONE for an unmatched row or a row of
+ *                             a short component, SGPU_TRACK_INCONSISTENT for a row of an
+ *                             inconsistent one
+ *   out_offsets [rows / 2 + 1], out_rows [rows]    both or neither: out_offsets[0 .. T] written,
+ *                             out_rows[out_offsets[t] .. out_offsets[t + 1]) = track t's rows in
+ *                             ascending order, which is set order
+ *   out_stats [4] or NULL     {components of >= 2 rows, tracks, inconsistent components, short
+ *                             components of >= 2 rows}
+ * The result is a pure function of the inputs.  All arrays are host memory.  Returns T or a
+ * negative error.
+ * SGPU_EINVAL, all checked on the host before anything is queued, no output byte written: NULL
+ * context, bad offsets or pair indices, a negative count, a match index outside its set,
+ * min_length < 2, rows >= 2^31, NULL out_track, exactly one of out_offsets / out_rows NULL, a NULL
+ * input that is needed.  SGPU_ENODEV: a device error, or the kernels' own termination check (a
+ * union-find step that did not move to a smaller row; never with intact memory).
+ * One upload (offsets, pair bases and matches in one block), at most two synchronisations; the
+ * number of launches, copies and synchronisations depends neither on npairs, nsets nor T.
+ * sgpu_last_timing's times[15] is the call's device time, from before its first kernel to after
+ * its last; every other slot is left as it was.  A repeated call of the same shape allocates
+ * nothing.
+ * sgpu_tracks_images: the sets are the last extract's images (image_pairs and matches as
+ * sgpu_match_images / sgpu_verify_images return them), with the error conditions of
+ * sgpu_match_images. */
+#define SGPU_TRACK_NONE (-1)
+#define SGPU_TRACK_INCONSISTENT (-2)
+int sgpu_tracks_batch(sgpu_ctx* ctx, const int64_t* set_offsets, int nsets,
+                      const int* set_pairs /* [npairs][2] */, int npairs,
+                      const int* matches /* [sum counts][2] */, const int* match_counts,
+                      int min_length,
+                      int* out_track /* [rows] */, int64_t* out_offsets /* [rows/2+1] or NULL */,
+                      int* out_rows /* [rows] or NULL */, long long* out_stats /* [4] or NULL */);
+int sgpu_tracks_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
+                       const int* matches, const int* match_counts, int min_length,
+                       int* out_track, int64_t* out_offsets, int* out_rows, long long* out_stats);
 
 #ifdef __cplusplus
 }

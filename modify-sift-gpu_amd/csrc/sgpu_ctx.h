@@ -62,7 +62,7 @@ struct DevBuf {
 // reference's "Detection" and "Feature List" stages, SiftPyramid.cpp:107,123); T_LIST is the
 // row-scan part of it
 enum { T_UPLOAD, T_PYRAMID, T_DETECT, T_ORIENT, T_EXPAND, T_DESC, T_DOWNLOAD, T_TOTAL, T_MATCH,
-       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_PREMATCH, T_N };
+       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_PREMATCH, T_TRACKS, T_N };
 
 // One part of a batch: consecutive images [img0, img0 + n) with their own stream and buffers.
 struct Part {
@@ -234,6 +234,11 @@ struct sgpu_ctx {
     sgplan::Plan p_hplan;
     std::vector<int64_t> p_sub;
     std::vector<int> p_pairs;
+    // track builder (sgpu_tracks_batch): the uploaded tables [set offsets][pair starts][pair bases]
+    // [matches], the work arrays and the scans' scratch, [out_offsets][out_track][out_rows][header];
+    // the tables as uploaded (alive until the call's first sync)
+    sgh::DevBuf t_tab, t_work, t_out;
+    std::vector<unsigned char> t_tables;
     // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
     // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
     sgh::DevBuf q_in, q_out, f_u8, f_s8, f_sums;

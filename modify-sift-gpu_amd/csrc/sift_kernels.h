@@ -568,4 +568,31 @@ hipError_t launch_gather_rows(const uint8_t* src, const int* src_terms, const lo
 hipError_t launch_remap_matches(const int* counts, const long long* offs, const int* pair_sub,
                                 const int* index, int npairs, long long cap, int* out,
                                 hipStream_t stream);
+
+// ---- feature tracks (sift_tracks.hip; sgpu_tracks_batch) ----
+// The call's header words on the device: the error flag (a loop met a step that does not move to a
+// smaller index, or a segment overflowed), the statistics' counters and the totals.
+enum { kTracksHdrErr, kTracksHdrComponents, kTracksHdrOversize, kTracksHdrShort,
+       kTracksHdrCandidates, kTracksHdrTracks, kTracksHdrTrackRows, kTracksHdrWords };
+// The uploaded tables: set offsets [nsets + 1], the scan of the match counts [npairs + 1], the two
+// sets' first rows of every pair [npairs][2], the matches [total][2].
+struct TracksTables {
+    const long long* set_off;
+    const long long* pair_start;
+    const int* pair_base;
+    const int* matches;
+};
+// Work arrays of `rows` words each (seg_start, toff, tid: rows + 1), scan_tmp of
+// scan_tmp_words(rows) words, hdr of kTracksHdrWords.
+struct TracksWork {
+    int *parent, *label, *seg, *sorted, *hdr;
+    uint32_t *size, *fill, *val, *seg_start, *tval, *tflag, *toff, *tid, *scan_tmp;
+};
+// The whole sequence on `stream` (rows > 0, nsets > 0; every index validated by the host): init,
+// union (total > 0), label, mark, scan, scatter, order, two scans, finish.  out_track [rows],
+// out_offsets [rows / 2 + 1] and out_rows [rows] are device buffers; hdr holds T and the rows of
+// all tracks afterwards.  The number of launches depends on rows alone.
+hipError_t launch_tracks(const TracksTables& tab, const TracksWork& w, long long rows, int nsets,
+                         int npairs, long long total, int min_length, int* out_track,
+                         long long* out_offsets, int* out_rows, hipStream_t stream);
 }  // namespace sgk

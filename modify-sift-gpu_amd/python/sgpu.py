@@ -4,6 +4,7 @@ The binding fails loudly when the library or a usable GPU is missing: there is n
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 import os
@@ -20,6 +21,7 @@ LIB_PATH = os.environ.get("SGPU_LIB_PATH") or os.path.join(PKG, "lib", "libsiftg
 
 SGPU_OK, SGPU_EINVAL, SGPU_ENODEV, SGPU_ENOMEM, SGPU_ERANGE = 0, -1, -2, -3, -4
 SGPU_INPUT_HOST, SGPU_INPUT_DEVICE, SGPU_INPUT_STAGED = 0, 1, 2
+SGPU_TRACK_NONE, SGPU_TRACK_INCONSISTENT = -1, -2
 
 # every extern "C" symbol include/sgpu.h declares (tests check the library exports them all)
 C_API = [
@@ -44,6 +46,7 @@ C_API = [
     "sgpu_select_top_scale_batch", "sgpu_select_top_scale_images",
     "sgpu_prematch_batch", "sgpu_prematch_images",
     "sgpu_debug_set_top_level", "sgpu_debug_top_level_at",
+    "sgpu_tracks_batch", "sgpu_tracks_images",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -154,6 +157,8 @@ def lib():
                                           c.c_float, c.c_float, c.c_int, vp, vp, c.c_int64, c.c_int]
         L.sgpu_prematch_images.argtypes = [vp, vp, c.c_int, c.c_int, c.c_float, c.c_float, c.c_int,
                                            vp, vp, c.c_int64]
+        L.sgpu_tracks_batch.argtypes = [vp, vp, c.c_int, vp, c.c_int, vp, vp, c.c_int, vp, vp, vp, vp]
+        L.sgpu_tracks_images.argtypes = [vp, vp, c.c_int, vp, vp, c.c_int, vp, vp, vp, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -233,6 +238,25 @@ def quantize_gpu(desc: np.ndarray, ctx: "SiftContext | None" = None) -> np.ndarr
     finally:
         if own:
             ctx.close()
+
+
+# What tracks_batch / tracks_images return: track_of_row [rows] int32 (the track id, SGPU_TRACK_NONE
+# or SGPU_TRACK_INCONSISTENT), offsets [T + 1] int64 and rows [offsets[T]] int32 (track t's rows =
+# rows[offsets[t]:offsets[t + 1]], ascending), stats [4] int64 = (components of >= 2 rows, tracks,
+# inconsistent components, short components of >= 2 rows).
+Tracks = collections.namedtuple("Tracks", "track_of_row offsets rows stats")
+
+
+def track_features(rows, offsets):
+    """Buffer rows -> (set, feature): the set s with offsets[s] <= row < offsets[s + 1] and the
+    row's index in it; two int arrays of rows' shape.  With the image offsets of a batch that is
+    (image, feature)."""
+    off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    r = np.asarray(rows, np.int64)
+    s = np.searchsorted(off, r, side="right") - 1
+    if len(r) and (len(off) < 2 or s.min() < 0 or r.max() >= off[-1]):
+        raise ValueError("a row lies outside the sets")
+    return s.astype(np.int32), (r - off[s]).astype(np.int32)
 
 
 class MatchOverflow(RuntimeError):
@@ -1008,6 +1032,72 @@ class SiftContext:
         t = np.zeros(15, np.float32)
         lib().sgpu_last_timing(self._ctx, t.ctypes.data, 15)
         return float(t[14])
+
+    # ---- feature tracks (sgpu_tracks_*)
+    @staticmethod
+    def _track_inputs(pairs, matches, min_length):
+        """The pair list and its per-pair [m, 2] matches as the C arrays: pairs [npairs][2],
+        the concatenated matches [total][2], counts [npairs]."""
+        pr = np.ascontiguousarray(pairs, np.int32)
+        if pr.size and (pr.ndim != 2 or pr.shape[1] != 2):
+            raise ValueError(f"pairs must be [npairs][2], got {pr.shape}")
+        pr = pr.reshape(-1, 2)
+        ms = [np.ascontiguousarray(m, np.int32) for m in matches]
+        if len(ms) != len(pr):
+            raise ValueError(f"{len(ms)} match lists for {len(pr)} pairs")
+        for m in ms:
+            if m.size and (m.ndim != 2 or m.shape[1] != 2):
+                raise ValueError(f"a pair's matches must be [m][2], got {m.shape}")
+        if int(min_length) < 2:
+            raise ValueError("min_length < 2")
+        counts = np.array([m.size // 2 for m in ms], np.int32)
+        flat = np.concatenate([m.reshape(-1, 2) for m in ms] + [np.zeros((0, 2), np.int32)])
+        return pr, np.ascontiguousarray(flat, np.int32), counts
+
+    def _tracks(self, call, rows, pairs, matches, min_length):
+        pr, flat, counts = self._track_inputs(pairs, matches, min_length)
+        track = np.zeros(max(rows, 1), np.int32)
+        offs = np.zeros(rows // 2 + 1, np.int64)
+        out = np.zeros(max(rows, 1), np.int32)
+        stats = np.zeros(4, np.int64)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        T = call(ptr(pr), len(pr), ptr(flat), ptr(counts), int(min_length), track.ctypes.data,
+                 offs.ctypes.data, out.ctypes.data, stats.ctypes.data)
+        if T < 0:
+            self._check(T, "tracks")
+        return Tracks(track[:rows].copy(), offs[:T + 1].copy(), out[:offs[T]].copy(), stats)
+
+    def tracks_batch(self, offsets, pairs, matches, min_length=2):
+        """Feature tracks of a pair list's matches (sgpu_tracks_batch; the rule of
+        csrc/sift_tracks.h): offsets and pairs as match_batch took them, matches the per-pair list
+        match_batch / match_batch_guided / verify_batch returned.  A track is a connected component
+        of the match graph with at least min_length rows and at most one row per set; tracks are
+        numbered in ascending order of their smallest row.  Returns Tracks(track_of_row, offsets,
+        rows, stats); track_features(rows, offsets) gives (set, feature)."""
+        off, nsets = self._set_offsets(offsets)
+        if (np.diff(off) < 0).any() or off[0] < 0:
+            raise ValueError("offsets must be non-negative and non-decreasing")
+
+        def call(pr, npairs, *rest):
+            return lib().sgpu_tracks_batch(self._ctx, off.ctypes.data, nsets, pr, npairs, *rest)
+        return self._tracks(call, int(off[-1]), pairs, matches, min_length)
+
+    def tracks_images(self, pairs, matches, min_length=2):
+        """tracks_batch over the last extract (sgpu_tracks_images): the sets are its images, pairs
+        and matches what match_images / verify_images took and returned.  track_features(rows,
+        image offsets) gives (image, feature)."""
+        rows = sum(self.count(i) for i in range(self.batch))
+
+        def call(pr, npairs, *rest):
+            return lib().sgpu_tracks_images(self._ctx, pr, npairs, *rest)
+        return self._tracks(call, rows, pairs, matches, min_length)
+
+    def tracks_time(self) -> float:
+        """Device milliseconds of the last tracks_batch / tracks_images (sgpu_last_timing's
+        times[15])."""
+        t = np.zeros(16, np.float32)
+        lib().sgpu_last_timing(self._ctx, t.ctypes.data, 16)
+        return float(t[15])
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
