@@ -386,7 +386,8 @@ int sgpu_estimate_images_refined(sgpu_ctx* ctx, const int* image_pairs, int npai
  * extract; times[8] = the last sgpu_match call; times[9] = the feature-list (row scan) part of
  * detect; times[10], [11] = the key and descriptor copies of the last sgpu_copy_features;
  * times[12] = the last sgpu_estimate_* call; times[13] = the last sgpu_verify_* call; times[14] =
- * the last sgpu_prematch_* call; times[15] = the last sgpu_tracks_* call.
+ * the last sgpu_prematch_* call; times[15] = the last sgpu_tracks_* call; times[16] = the last
+ * sgpu_pose_* call.
  * SiftGPU::_timing[2..8] map them to the reference's slots (siftgpu_api.cpp).  Slots 0-7 and
  * 9-11 read 0 after a one-stream extract / copy made with the stage timing off. */
 int sgpu_last_timing(const sgpu_ctx* ctx, float* times, int n);
@@ -735,6 +736,69 @@ int sgpu_tracks_batch(sgpu_ctx* ctx, const int64_t* set_offsets, int nsets,
 int sgpu_tracks_images(sgpu_ctx* ctx, const int* image_pairs, int npairs,
                        const int* matches, const int* match_counts, int min_length,
                        int* out_track, int64_t* out_offsets, int* out_rows, long long* out_stats);
+
+/* Relative pose and triangulation of verified pairs, on the device: the two-view step between a
+ * pair's F (sgpu_estimate_* / sgpu_verify_*) and a reconstruction.  It says which of the four
+ * decompositions of the pair's essential matrix is the physical one, how many matches lie in front
+ * of both cameras and how many of those have a useful triangulation angle: what an initial pair is
+ * chosen by, and what tells a pure rotation or a plane from a pair with a baseline.  No reference
+ * counterpart in SiftGPU.
+ *
+ * loc, set_offsets, set_pairs, matches, match_counts, flags: exactly those of sgpu_estimate_batch
+ * (loc host memory, or device memory with SGPU_INPUT_DEVICE; everything else host memory).
+ * intrinsics[s] = {fx, fy, cx, cy} of set s: a pinhole camera without skew or distortion.  F + 9 p
+ * = pair p's fundamental matrix as sgpu_estimate_* / sgpu_verify_* return it: set a is the first
+ * view, x2' F x1 = 0.
+ *
+ * Rule (csrc/sift_pose.h defines the arithmetic, all of it in double):
+ *  - a match participates when the guided matcher's own float test holds for it: Sampson error
+ *    under F_p < f_threshold (squared pixels).  The matches of a guided pass under that F all
+ *    participate; 1e20 takes every match;
+ *  - E = K2' F K1 at unit Frobenius norm is decomposed through the eigenvectors of E'E (cyclic
+ *    Jacobi, a fixed order and number of sweeps): E = U diag(s1, s2, .) V' with right-handed U and
+ *    V.  No pose when F is zero or not finite, or when s2 is not above 1e-3 s1 (a rank-1 F);
+ *  - the candidates, in this order: (U W V', +u3), (U W V', -u3), (U W' V', +u3), (U W' V', -u3),
+ *    W = [0 -1 0; 1 0 0; 0 0 1]; every R has determinant +1;
+ *  - a participant is triangulated under (R, t) by the midpoint method: rays a = inv(K1) (x1, y1,
+ *    1), b = inv(K2) (x2, y2, 1), c = R a, depths l1, l2 from the normal equations of
+ *    l1 c - l2 b = -t.  In front: |c x b|^2 > 1e-12, l1 > 0 and l2 > 0.  Its point is
+ *    X = (l1 a + R' (l2 b - t)) / 2, in the first camera's frame at |t| = 1.  An in-front match is
+ *    wide when the angle between c and b is at least min_angle (radians; cosines are compared);
+ *  - the winner is the candidate with the most participants in front, the lowest index among
+ *    equal counts.
+ *   out_R [npairs][9], out_t [npairs][3]   the winner's R (row-major) and unit t, as float:
+ *                                 x_cam2 = R x_cam1 + t
+ *   out_counts [npairs][3]        {participants, in front under the winner, wide under the winner}
+ *   out_mask [sum counts] or NULL     1 for a participant in front under the winner
+ *   out_points [sum counts][3] or NULL   that match's X; zeros for every other match
+ * A pair without a pose, without a participant or whose best count is 0 gets zeros for R, t, mask
+ * and points, and counts {participants, 0, 0}.  The result is a pure function of the inputs.
+ * SGPU_EINVAL, all checked on the host before anything is queued, no output byte written: every
+ * argument error of sgpu_estimate_batch for the shared arguments; NULL F, intrinsics, out_R, out_t
+ * or out_counts with pairs present; an intrinsic row of a set that some pair names with an entry
+ * that is not finite or with fx, fy <= 0; a negative or non-finite f_threshold; min_angle outside
+ * [0, pi/2].
+ * One table upload (pair records, matches, F and intrinsics in one block), one download, one
+ * synchronisation; the number of launches, copies and synchronisations does not depend on npairs.
+ * sgpu_last_timing's times[16] is the call's device time; every other slot is left as it was.  A
+ * repeated call of the same shape allocates nothing.
+ * sgpu_pose_images: over the last extract.  The sets are the batch's images, the locations x, y of
+ * its device keys (a multi-part batch: the gathered key buffer); error conditions of
+ * sgpu_estimate_images. */
+int sgpu_pose_batch(sgpu_ctx* ctx, const float* loc, const int64_t* set_offsets, int nsets,
+                    const float* intrinsics /* [nsets][4]: fx, fy, cx, cy */,
+                    const int* set_pairs /* [npairs][2] */, int npairs,
+                    const int* matches /* [sum counts][2] */, const int* match_counts,
+                    const float* F /* [npairs][9] */, float f_threshold, float min_angle /* rad */,
+                    float* out_R /* [npairs][9] */, float* out_t /* [npairs][3] */,
+                    int* out_counts /* [npairs][3]: participants, front, wide */,
+                    uint8_t* out_mask /* [sum counts] or NULL */,
+                    float* out_points /* [sum counts][3] or NULL */, int flags);
+int sgpu_pose_images(sgpu_ctx* ctx, const float* intrinsics /* [batch][4] */,
+                     const int* image_pairs, int npairs, const int* matches,
+                     const int* match_counts, const float* F, float f_threshold, float min_angle,
+                     float* out_R, float* out_t, int* out_counts, uint8_t* out_mask,
+                     float* out_points);
 
 #ifdef __cplusplus
 }

@@ -322,7 +322,7 @@ int sgpu_ctx_destroy(sgpu_ctx* ctx) {
                       &ctx->b_cnt, &ctx->b_out, &ctx->b_loc, &ctx->q_in, &ctx->q_out, &ctx->f_u8, &ctx->f_s8,
                       &ctx->f_sums, &ctx->c_buf, &ctx->e_loc, &ctx->e_plan, &ctx->e_pts, &ctx->e_slots,
                       &ctx->e_out, &ctx->e_mask, &ctx->v_buf, &ctx->p_scale, &ctx->p_index, &ctx->p_u8,
-                      &ctx->t_tab, &ctx->t_work, &ctx->t_out};
+                      &ctx->t_tab, &ctx->t_work, &ctx->t_out, &ctx->o_tab, &ctx->o_out};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i <= T_N; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);

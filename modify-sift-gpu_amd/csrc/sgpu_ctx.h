@@ -62,7 +62,8 @@ struct DevBuf {
 // reference's "Detection" and "Feature List" stages, SiftPyramid.cpp:107,123); T_LIST is the
 // row-scan part of it
 enum { T_UPLOAD, T_PYRAMID, T_DETECT, T_ORIENT, T_EXPAND, T_DESC, T_DOWNLOAD, T_TOTAL, T_MATCH,
-       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_PREMATCH, T_TRACKS, T_N };
+       T_LIST, T_COPY_KEYS, T_COPY_DESC, T_ESTIMATE, T_VERIFY, T_PREMATCH, T_TRACKS, T_POSE,
+       T_N };
 
 // One part of a batch: consecutive images [img0, img0 + n) with their own stream and buffers.
 struct Part {
@@ -239,6 +240,12 @@ struct sgpu_ctx {
     // the tables as uploaded (alive until the call's first sync)
     sgh::DevBuf t_tab, t_work, t_out;
     std::vector<unsigned char> t_tables;
+    // relative pose (sgpu_pose_batch; the estimator's e_loc, e_pts and e_hplan above carry its
+    // uploaded locations, float4 rows and pair records): the uploaded tables [pairs][matches][set
+    // pairs][F][intrinsics], [R][t][counts][points][mask]; the tables as uploaded (alive until the
+    // call's sync) and the result block's host copy
+    sgh::DevBuf o_tab, o_out;
+    std::vector<unsigned char> o_tables, o_result;
     // device quantiser: staging of a host-pointer sgpu_quantize_descriptors_gpu, and the last
     // extract's descriptors as u8 / s8 / row sums (sgpu_feature_descriptors_u8; valid while f_ready)
     sgh::DevBuf q_in, q_out, f_u8, f_s8, f_sums;

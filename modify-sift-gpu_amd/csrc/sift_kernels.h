@@ -595,4 +595,26 @@ struct TracksWork {
 hipError_t launch_tracks(const TracksTables& tab, const TracksWork& w, long long rows, int nsets,
                          int npairs, long long total, int min_length, int* out_track,
                          long long* out_offsets, int* out_rows, hipStream_t stream);
+
+// ---- relative pose of verified pairs (sift_pose.hip; sgpu_pose_batch) ----
+// What k_pose reads and writes, all device memory.  pts: launch_estimate_gather's rows; set_pairs
+// [npairs][2], intrinsics [nsets][4], F [npairs][9].  R [npairs][9], t [npairs][3], counts
+// [npairs][3], mask [total] (may be null), points [total][3] (may be null): every output byte must
+// be zero beforehand, the kernel stores the non-zero values only.
+struct PoseArgs {
+    const float4* pts;
+    const sgeo::PairRec* pairs;
+    const int* set_pairs;
+    const float* intrinsics;
+    const float* F;
+    float* R;
+    float* t;
+    int* counts;
+    uint8_t* mask;
+    float* points;
+};
+// One wave per pair, a grid-stride over the pairs: the arithmetic of sift_pose.h.  cos_min =
+// spose::cos_min_angle(min_angle), taken on the host.
+hipError_t launch_pose(const PoseArgs& a, int npairs, float f_threshold, double cos_min,
+                       hipStream_t stream);
 }  // namespace sgk

@@ -47,6 +47,7 @@ C_API = [
     "sgpu_prematch_batch", "sgpu_prematch_images",
     "sgpu_debug_set_top_level", "sgpu_debug_top_level_at",
     "sgpu_tracks_batch", "sgpu_tracks_images",
+    "sgpu_pose_batch", "sgpu_pose_images",
 ]
 
 # launch kinds of SiftContext.pyramid_plan() (SGPU_PLAN_* of sgpu.h, in their order)
@@ -159,6 +160,10 @@ def lib():
                                            vp, vp, c.c_int64]
         L.sgpu_tracks_batch.argtypes = [vp, vp, c.c_int, vp, c.c_int, vp, vp, c.c_int, vp, vp, vp, vp]
         L.sgpu_tracks_images.argtypes = [vp, vp, c.c_int, vp, vp, c.c_int, vp, vp, vp, vp]
+        L.sgpu_pose_batch.argtypes = [vp, vp, vp, c.c_int, vp, vp, c.c_int, vp, vp, vp, c.c_float,
+                                      c.c_float, vp, vp, vp, vp, vp, c.c_int]
+        L.sgpu_pose_images.argtypes = [vp, vp, vp, c.c_int, vp, vp, vp, c.c_float, c.c_float, vp, vp,
+                                       vp, vp, vp]
         L.sgpu_debug_match_plan_stats.argtypes = [vp, vp]
         L.sgpu_debug_pyramid_plan.argtypes = [vp, vp, c.c_int]
         _LIB = L
@@ -245,6 +250,10 @@ def quantize_gpu(desc: np.ndarray, ctx: "SiftContext | None" = None) -> np.ndarr
 # rows[offsets[t]:offsets[t + 1]], ascending), stats [4] int64 = (components of >= 2 rows, tracks,
 # inconsistent components, short components of >= 2 rows).
 Tracks = collections.namedtuple("Tracks", "track_of_row offsets rows stats")
+# what pose_batch / pose_images return: R [npairs][3][3], t [npairs][3] (float32), participants /
+# front / wide [npairs] (int32), masks: one bool array per pair, points: one [m][3] float32 array
+# per pair (None for points=False)
+Pose = collections.namedtuple("Pose", "R t participants front wide masks points")
 
 
 def track_features(rows, offsets):
@@ -1098,6 +1107,94 @@ class SiftContext:
         t = np.zeros(16, np.float32)
         lib().sgpu_last_timing(self._ctx, t.ctypes.data, 16)
         return float(t[15])
+
+    # ---- relative pose of verified pairs (sgpu_pose_*)
+    DEFAULT_MIN_ANGLE = float(np.deg2rad(2.0))
+
+    @staticmethod
+    def _pose_inputs(pairs, matches, F, K, nsets, threshold, min_angle):
+        """The pair list, its per-pair [m, 2] matches, the pairs' F and the sets' intrinsics as the
+        C arrays; every shape error is a ValueError here, before any C call."""
+        pr = np.ascontiguousarray(pairs, np.int32)
+        if pr.size and (pr.ndim != 2 or pr.shape[1] != 2):
+            raise ValueError(f"pairs must be [npairs][2], got {pr.shape}")
+        pr = pr.reshape(-1, 2)
+        npairs = len(pr)
+        if len(matches) != npairs:
+            raise ValueError(f"{npairs} pairs but {len(matches)} match arrays")
+        ms = [np.ascontiguousarray(m, np.int32) for m in matches]
+        for m in ms:
+            if m.size and (m.ndim != 2 or m.shape[1] != 2):
+                raise ValueError(f"a pair's matches must be [m][2], got {m.shape}")
+        fm = np.ascontiguousarray(F, np.float32)
+        if fm.size != 9 * npairs or (npairs and fm.shape not in ((npairs, 3, 3), (npairs, 9))):
+            raise ValueError(f"F must be [{npairs}][3][3], got {fm.shape}")
+        km = np.ascontiguousarray(K, np.float32)
+        if km.ndim != 2 or km.shape[1] != 4 or (nsets is not None and len(km) != nsets):
+            raise ValueError(f"K must be [sets][4] (fx, fy, cx, cy), got {km.shape}")
+        if not (float(threshold) >= 0 and np.isfinite(threshold)):
+            raise ValueError("threshold negative or not finite")
+        if not 0 <= float(min_angle) <= np.pi / 2 + 1e-7:
+            raise ValueError("min_angle outside [0, pi/2]")
+        counts = np.array([m.size // 2 for m in ms], np.int32)
+        flat = np.concatenate([m.reshape(-1, 2) for m in ms] + [np.zeros((0, 2), np.int32)])
+        return pr, np.ascontiguousarray(flat, np.int32), counts, fm.reshape(-1, 9), km
+
+    def _pose(self, call, inputs, threshold, min_angle, points):
+        pr, flat, counts, fm, km = inputs
+        npairs, total = len(pr), len(flat)
+        R = np.zeros((max(npairs, 1), 9), np.float32)
+        t = np.zeros((max(npairs, 1), 3), np.float32)
+        oc = np.zeros((max(npairs, 1), 3), np.int32)
+        mask = np.zeros(max(total, 1), np.uint8)
+        pts = np.zeros((max(total, 1), 3), np.float32) if points else None
+        ptr = lambda a: a.ctypes.data if a.size else None
+        rc = call(ptr(km), ptr(pr), npairs, ptr(flat), ptr(counts), ptr(fm), float(threshold),
+                  float(min_angle), R.ctypes.data, t.ctypes.data, oc.ctypes.data, mask.ctypes.data,
+                  pts.ctypes.data if points else None)
+        self._check(rc, "pose")
+        offs = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        masks = [mask[offs[p]:offs[p + 1]].astype(bool) for p in range(npairs)]
+        plist = [pts[offs[p]:offs[p + 1]].copy() for p in range(npairs)] if points else None
+        return Pose(R[:npairs].reshape(npairs, 3, 3).copy(), t[:npairs].copy(), oc[:npairs, 0].copy(),
+                    oc[:npairs, 1].copy(), oc[:npairs, 2].copy(), masks, plist)
+
+    def pose_batch(self, loc: np.ndarray, offsets, pairs, matches, F, K, threshold=4.0,
+                   min_angle=DEFAULT_MIN_ANGLE, points=True, device_ptr=None):
+        """Relative pose and triangulation of every pair (sgpu_pose_batch; the rule of
+        csrc/sift_pose.h): loc, offsets, pairs and matches as estimate_batch took them, F
+        [npairs][3][3] as estimate_batch / verify_batch returned it, K [sets][4] = (fx, fy, cx, cy).
+        A match participates when its Sampson error under F is below threshold; the pair's E is
+        decomposed, and the candidate (R, t) with the most participants in front of both cameras
+        wins.  Returns Pose(R, t, participants, front, wide, masks, points): x_cam2 = R x_cam1 + t
+        with |t| = 1; wide counts the in-front matches whose rays meet at min_angle (radians) or
+        more; masks[p] marks the in-front participants, points[p] their X in the first camera's
+        frame (zeros elsewhere; None with points=False).  A pair without a pose has zeros."""
+        off, nsets, lc, ptr, flags = self._estimate_sets(loc, offsets, device_ptr)
+        inputs = self._pose_inputs(pairs, matches, F, K, nsets, threshold, min_angle)
+
+        def call(km, pr, npairs, *rest):
+            return lib().sgpu_pose_batch(self._ctx, ptr, off.ctypes.data, nsets, km, pr, npairs,
+                                         *rest, flags)
+        return self._pose(call, inputs, threshold, min_angle, points)
+
+    def pose_images(self, pairs, matches, F, K, threshold=4.0, min_angle=DEFAULT_MIN_ANGLE,
+                    points=True):
+        """pose_batch over the last extract (sgpu_pose_images): the sets are its images, K
+        [batch][4]; the locations are the batch's device keys and stay in HBM."""
+        batch = getattr(self, "batch", 0) or None   # without a batch the call itself refuses
+        inputs = self._pose_inputs(pairs, matches, F, K, batch, threshold, min_angle)
+
+        def call(km, pr, npairs, *rest):
+            return lib().sgpu_pose_images(self._ctx, km, pr, npairs, *rest)
+        return self._pose(call, inputs, threshold, min_angle, points)
+
+    def pose_time(self) -> float:
+        """Device milliseconds of the last pose_batch / pose_images (sgpu_last_timing's
+        times[16])."""
+        t = np.zeros(17, np.float32)
+        lib().sgpu_last_timing(self._ctx, t.ctypes.data, 17)
+        return float(t[16])
 
     def match_guided(self, d1: np.ndarray, d2: np.ndarray, loc1: np.ndarray, loc2: np.ndarray,
                      H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
